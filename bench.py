@@ -1,12 +1,18 @@
 """bench.py -- scored triples/sec of the all-entities evaluation hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Both forms work for N > 1: started WITHOUT a launcher (no WORLD_SIZE in the environment), `python bench.py --gpus N`
 starts its own N ranks (torch.distributed.run on 127.0.0.1 and a free port), passes rank 0's single JSON line through and
 exits with the launcher's status (non-zero if any rank died).
+
+A plain run sets the workload up, warms up, times K steps and prints one JSON line: `value` (scored triples/s over the K
+steps), `ms_per_step`, the metrics of the last step.  --dump-outputs DIR also writes what the last timed step returned
+(dump_outputs).  Everything else -- raw-only step, kernel time and roofline, the parity spot check against the CPU oracle, the
+CPU and stock-PyTorch baselines, the sub-results, the in-batch loss, call overhead, table build, the HBM probe and the details
+file -- takes runs of its own and comes with --full.
 
 A "step" is ONE WHOLE EVALUATION of the workload's test triples against the entity table, exactly what
 blp_amd.ranking.eval_link_prediction runs after the table build (it is the same function,
@@ -32,7 +38,7 @@ Workloads (synthetic data of the published shapes, seeded; BASELINE.json configs
   wikidata5m-protocol   the reference's OWN Wikidata5M candidate set (train.py:312-314: only the 7 475 entities of the test
                     split), 6 894 triples; also timed in the reference loop's layout (eval_batch_size = 2: 3 447 batches
                     through ONE blp_rank_all_batches call, and with a ranking pass per batch)
-The default run reports fb15k237-distmult, fb15k237-complex, wikidata5m-transe (reference batching, with its filter),
+The default run with --full reports fb15k237-distmult, fb15k237-complex, wikidata5m-transe (reference batching, with its filter),
 wikidata5m-complex, wikidata5m-transe-block, wikidata5m-complex-block, wikidata5m-transe-full, wikidata5m-complex-full and
 wikidata5m-protocol as `sub_results` (each with its own roofline), the training-side step as `inbatch_loss` and the
 HBM-bound operating point as `hbm_probe` -- THE SAME NAMES for every N, so that the N = 1 line of a scaling run can be held
@@ -560,39 +566,42 @@ class Job:
         roof["algorithmic_flops_per_launch"] = alg_flops
         return roof
 
-    def measure(self, steps, warmup, events):
-        """The JSON fields of this workload: whole evaluation (raw + filtered) and raw-only, the roofline."""
-        if self.heavy:  # a step takes seconds: two timed steps (one on several GPUs), one of everything else
-            cap_steps, cap_warmup = heavy_steps(self.world)
-            steps, warmup = min(steps, cap_steps), min(warmup, cap_warmup)
-        raw_steps = 1 if self.heavy else max(1, min(steps, 5))
+    def measure(self, steps, warmup, events=None):
+        """The JSON fields of this workload: the whole evaluation (raw + filtered) timed over `steps` steps and the metrics of
+        the last one.  With `events` (bench.py --full) also the raw-only step, the ranking pass's kernel time, the exchanges
+        and the roofline, each from runs of their own after the timed ones.  Returns (fields, triples, counts, sums) of the
+        last timed step."""
         elapsed, (triples, counts, sums) = self.timed(steps, warmup, filtered=True)
+        host_sums = sums.cpu()
+        out = {
+            "value": 2.0 * self.T * self.N * steps / elapsed,
+            "ms_per_step": elapsed / steps * 1e3, "timed_steps": steps,
+            "mrr": host_sums[0].item() / (2 * self.T), "mrr_filtered": host_sums[1].item() / (2 * self.T),
+            "hits@1,3,10": [x.item() / (2 * self.T) for x in host_sums[2:5]],
+            "hits@1,3,10_filtered": [x.item() / (2 * self.T) for x in host_sums[5:8]],
+            "filter_index_build_ms": self.filter_index_build_ms,  # once per evaluation set-up, NOT inside ms_per_step
+            "filter_index_first_build_ms_in_this_process": self.filter_index_first_build_ms,  # (+ loading the sort's code objects)
+            "filter_index_edges": self.index.num_edges,
+        }
+        if events is None:
+            return out, triples, counts, sums
+        raw_steps = 1 if self.heavy else max(1, min(steps, 5))
         raw_elapsed, _ = self.timed(raw_steps, 0 if self.heavy else 1, filtered=False)
         kernel_ms = self.kernel_ms(events, 1 if self.heavy else max(1, min(steps, 10)))
         exchange = self.exchange_ms(1 if self.heavy else max(1, min(steps, 5)))
-        scored = 2.0 * self.T * self.N
         per_rank, exchange_per_rank = [kernel_ms], [exchange]
         if self.world > 1:
             box = [None] * self.world
             dist.all_gather_object(box, (kernel_ms, exchange))
             per_rank, exchange_per_rank = [b[0] for b in box], [b[1] for b in box]
-        sums = sums.cpu()
-        out = {
-            "value": scored * steps / elapsed,
-            "ms_per_step": elapsed / steps * 1e3,
-            "ms_per_step_raw_only": raw_elapsed / raw_steps * 1e3, "timed_steps": steps,
-            "mrr": sums[0].item() / (2 * self.T), "mrr_filtered": sums[1].item() / (2 * self.T),
-            "hits@1,3,10": [x.item() / (2 * self.T) for x in sums[2:5]],
-            "hits@1,3,10_filtered": [x.item() / (2 * self.T) for x in sums[5:8]],
+        out.update({
+            "ms_per_step_raw_only": raw_elapsed / raw_steps * 1e3,
             "roofline": self.roofline(kernel_ms),
             "kernel_ms_per_rank": per_rank,
             "exchange_ms": max(exchange_per_rank), "exchange_ms_per_rank": exchange_per_rank,
             "shard_axis": self.axis, "ranks": self.world,
-            "filter_index_build_ms": self.filter_index_build_ms,  # once per evaluation set-up, NOT inside ms_per_step
-            "filter_index_first_build_ms_in_this_process": self.filter_index_first_build_ms,  # (+ loading the sort's code objects)
-            "filter_index_edges": self.index.num_edges,
-        }
-        return out, triples, counts
+        })
+        return out, triples, counts, sums
 
 
 def cpu_model_name():
@@ -1049,13 +1058,16 @@ def relaunch_with_ranks(n_gpus, timeout_s=None):
 def sub_result(name, axis, device, world, rank, backend, steps, events):
     """One sub-result: the workload prepared, measured (the better of two timed runs on one GPU) and torn down."""
     sub = Job(name, device, world, rank, axis, backend)
-    k_sub = max(2, min(steps, 5))
+    k_sub, warm = max(2, min(steps, 5)), 3 if world == 1 else 1
+    if sub.heavy:  # a step takes seconds: two timed steps (one on several GPUs), one of everything else
+        cap_steps, cap_warmup = heavy_steps(world)
+        k_sub, warm = min(k_sub, cap_steps), min(warm, cap_warmup)
     # best of two timed runs of K steps: a one-off stall (a code object loaded on first use, the allocator growing)
     # inside a 5-step run once made a 1.2 ms evaluation read as 16 ms
-    f, t, c = sub.measure(k_sub, 3 if world == 1 else 1, events)
+    f, t, c, _ = sub.measure(k_sub, warm, events)
     runs = 1
     if world == 1 and not sub.heavy:
-        f2, t2, c2 = sub.measure(k_sub, 1, events)
+        f2, t2, c2, _ = sub.measure(k_sub, 1, events)
         runs = 2
         if f2["ms_per_step"] < f["ms_per_step"]:
             f, t, c = f2, t2, c2
@@ -1250,7 +1262,8 @@ def compact_result(result, limit=LINE_LIMIT):
     world = result.get("n_gpus", 1)
     line = {k: result[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                                    "scaling", "vs_baseline", "dtype", "data") if k in result}
-    line["arith"] = _short(result.get("arith"), 120)
+    if "arith" in result:
+        line["arith"] = _short(result["arith"], 120)
     cfg = dict(result.get("config", {}))
     cfg.pop("step", None)
     line["config"] = cfg
@@ -1258,7 +1271,8 @@ def compact_result(result, limit=LINE_LIMIT):
               "filter_index_build_ms", "vs_1gpu", "kernel_ms_per_rank", "exchange_ms_per_rank"):
         if k in result:
             line[k] = result[k]
-    line["roofline"] = compact_roofline(result.get("roofline"))
+    if "roofline" in result:
+        line["roofline"] = compact_roofline(result["roofline"])
     cpu = result.get("cpu_baseline")
     if cpu:
         line["cpu_baseline"] = {"value": cpu["value"], "unit": cpu["unit"], "cores": cpu["cores"], "kind": _short(cpu["kind"], 40),
@@ -1277,7 +1291,8 @@ def compact_result(result, limit=LINE_LIMIT):
         line["hbm_probe"] = {k: result["hbm_probe"].get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "kernel_ms", "traffic")}
     if "call_overhead" in result:
         line["call_overhead"] = {k: result["call_overhead"].get(k) for k in ("library_call_us", "rank_all_128_queries_fb15k237_us")}
-    line["details"] = result.get("details")
+    if "details" in result:
+        line["details"] = result["details"]
     line = _sig(line)
     line["value"], line["ms_per_step"] = result["value"], result["ms_per_step"]  # (full precision: value == units / time, to the bit)
     for drop in ("call_overhead", "torch_gpu_baseline_value", "inbatch_loss", "hbm_probe", "hits@1,3,10", "hits@1,3,10_filtered"):
@@ -1301,6 +1316,23 @@ def write_details(result, path):
     except OSError as exc:  # (a read-only tree: the compact line must still be printed)
         print(f"bench.py: could not write {path}: {exc}", file=sys.stderr)
         return None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, counts, sums):
+    """--dump-outputs DIR: what the last timed step returned to its caller (ranking.rank_triples + ops.rank_metric_sums), as
+    float64 .npy files -- counts.npy, the (2T, 4) int32 rank counts of every query (all head queries first; exact in float64)
+    and metric_sums.npy, the 8 sums the line's MRR / Hits@k come from.  The inputs are seeded: the same arguments give the
+    same inputs in every run, so that two builds can be compared output for output."""
+    import numpy as np
+    arrays = {"counts": counts.double().cpu().numpy(), "metric_sums": sums.double().cpu().numpy()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes, over the {DUMP_LIMIT_BYTES} byte limit"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def dry_run_collectives(device, world, rank, backend, result_fd, nbytes=1024, timeout_s=120):
@@ -1365,17 +1397,26 @@ def main():
                          "candidate axis -- on several)")
     ap.add_argument("--dry-nccl", action="store_true", help="pre-flight of an N > 1 run: bring the process group up, run the three "
                     "collectives of an evaluation on 1 KB each, print one JSON line and exit (a failing rank is named, status 3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-hbm-probe", action="store_true")
-    ap.add_argument("--no-sub-results", action="store_true")
-    ap.add_argument("--details", default=os.path.join(ROOT, DETAILS_FILE),
-                    help="where rank 0 writes the FULL result object (the stdout line is its compact form, < 6 KB)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: raw-only step, kernel time and roofline, parity check against the CPU "
+                         "oracle, CPU and stock-PyTorch baselines, sub-results, in-batch loss, call overhead, table build, HBM "
+                         "probe, and the details file (default: set up, warm up, time --steps steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) without the CPU and stock-PyTorch baselines")
+    ap.add_argument("--no-hbm-probe", action="store_true", help="(--full) without the HBM probe")
+    ap.add_argument("--no-sub-results", action="store_true", help="(--full) without the sub-results and the other side figures")
+    ap.add_argument("--details", default=None,
+                    help="where rank 0 writes the FULL result object (the stdout line is its compact form, < 6 KB); default "
+                         f"with --full: {DETAILS_FILE} next to bench.py, none without it")
     ap.add_argument("--shard-axis", default="auto", choices=["auto", "candidate", "query"],
                     help="N > 1: which axis to shard (default: blp_amd.ranking.choose_shard_axis; the Wikidata5M-scale "
                          "table always along the candidate axis)")
     ap.add_argument("--plan", action="store_true", help="print what a run on --gpus N ranks would do (axes, shards, the bytes of "
                     "every collective, steps of the long workloads) as JSON and exit; needs no GPU")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     default_line = args.workload is None
     if default_line:
         args.workload = headline_workload(args.gpus)
@@ -1422,10 +1463,12 @@ def main():
             dist.init_process_group("nccl", device_id=device)
         ranks_seen = dist.get_world_size()
 
-    events = HipEvents()
+    events = HipEvents() if args.full else None
     job = Job(args.workload, device, world, rank, args.shard_axis, backend)
-    fields, triples, counts = job.measure(args.steps, args.warmup, events)
-    timed_steps = fields.pop("timed_steps")  # (== --steps, except for the whole-evaluation workloads: two steps of > 1 s)
+    fields, triples, counts, sums = job.measure(args.steps, args.warmup, events)
+    timed_steps = fields.pop("timed_steps")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, counts, sums)
     cfg = job.cfg
     result = None
     if rank == 0:
@@ -1441,7 +1484,6 @@ def main():
             "scaling": "strong",
             "vs_baseline": None,
             "dtype": "f32",
-            "arith": fields["roofline"]["arith"],
             "data": "synthetic (seeded randn table, Xavier rel_emb, uniform random test triples, Zipf(0.8) filtering graph)",
             "config": {"workload": args.workload, "rel_model": cfg["model"], "entities": cfg["N"], "dim": cfg["D"],
                        "queries_per_step": 2 * cfg["triples"], "triples_per_ranking_call": min(cfg["triples"], cfg["block"]),
@@ -1452,6 +1494,8 @@ def main():
                        "shard_axis": job.axis, "ranks_in_process_group": ranks_seen, "backend": backend if world > 1 else None},
         }
         result.update(fields)
+    if args.full and rank == 0:
+        result["arith"] = result["roofline"]["arith"]
         if world > 1:  # against the committed one-GPU run of the SAME workload (the driver computes its own efficiency from its N = 1 line)
             ref = n1_reference(args.workload)
             result["vs_1gpu"] = result["value"] / ref["value"] if ref else None
@@ -1464,9 +1508,9 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(job)
             result["torch_gpu_baseline"] = torch_gpu_baseline(job)
-    del triples, counts, job
+    del triples, counts, sums, job
     torch.cuda.empty_cache()
-    if not args.no_sub_results and default_line:
+    if args.full and not args.no_sub_results and default_line:
         # The same names for every N (SCALE's N = 1 line against BENCH, field by field).  N > 1: every rank takes part in
         # every sub-result -- each step has its exchanges (replicated query vectors, one all-gather of counts).
         subs = {}
@@ -1492,12 +1536,14 @@ def main():
             result["sub_results"], result["inbatch_loss"] = subs, inbatch
             result["call_overhead"] = call_overhead(device)
             result["table_build"] = table_build_bench(device)
-    if not args.no_hbm_probe and (default_line or not args.workload.startswith("wikidata5m")):
+    if args.full and not args.no_hbm_probe and (default_line or not args.workload.startswith("wikidata5m")):
         if rank == 0:  # one GPU's HBM-bound operating point (the other ranks wait at the barrier below)
             result["hbm_probe"] = hbm_probe(device, events)
     if rank == 0:
-        written = write_details(result, args.details)
-        result["details"] = os.path.relpath(written, ROOT) if written else None
+        details = args.details or (os.path.join(ROOT, DETAILS_FILE) if args.full else None)
+        if details:
+            written = write_details(result, details)
+            result["details"] = os.path.relpath(written, ROOT) if written else None
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(compact_result(result)) + "\n").encode())
     if world > 1:

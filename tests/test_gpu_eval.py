@@ -163,7 +163,7 @@ def test_bench_two_ranks_share_one_gpu_functional(axis, tmp_path):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--steps", "1", "--warmup", "0", "--workload", "fb15k237-transe", "--no-cpu-baseline", "--no-hbm-probe",
+    common = ["--steps", "1", "--warmup", "0", "--workload", "fb15k237-transe", "--full", "--no-cpu-baseline", "--no-hbm-probe",
               "--no-sub-results"]
     one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), *common, "--details", str(tmp_path / "one.json")],
                          capture_output=True, text=True, timeout=600, cwd=root)
@@ -188,7 +188,7 @@ def test_bench_two_ranks_share_one_gpu_functional(axis, tmp_path):
 
 @pytest.mark.default_routing
 def test_bench_default_two_rank_line_reports_the_candidate_axis_too(tmp_path):
-    """The line the driver gets from `python bench.py --gpus N` with its defaults, started WITHOUT a launcher (round 3's
+    """The line the driver gets from `python bench.py --gpus N --full`, started WITHOUT a launcher (round 3's
     bench.py exited asking for torch.distributed.run): here N = 2 over gloo on this one GPU.  bench.py starts its own two
     ranks; ONE JSON line comes back; its TOP LEVEL is the quantity the north_star's scaling target is defined on -- the
     Wikidata5M-scale TransE ranking in the reference's batching on the CANDIDATE axis (shards of the table, each rank
@@ -203,7 +203,7 @@ def test_bench_default_two_rank_line_reports_the_candidate_axis_too(tmp_path):
     env = dict(os.environ, BLP_BENCH_BACKEND="gloo")
     for key in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(key, None)
-    two = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    two = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
                           "--details", str(tmp_path / "two.json")], capture_output=True, text=True, timeout=2400, cwd=root, env=env)
     assert two.returncode == 0, two.stderr[-2000:]
     lines = [l for l in two.stdout.strip().splitlines() if l.startswith("{")]
@@ -256,7 +256,7 @@ def test_bench_default_two_rank_line_reports_the_candidate_axis_too(tmp_path):
 
 @pytest.mark.default_routing
 def test_bench_line_keeps_the_contract(tmp_path):
-    """`python bench.py` with its defaults: ONE JSON line on stdout with the driver's keys; the step is the whole
+    """`python bench.py --full`: ONE JSON line on stdout with the driver's keys; the step is the whole
     evaluation (raw + filtered), with the raw-only time beside it; the roofline of the dominant kernel; the CPU
     baseline on all threads and on one, with the CPU model; driver-timed sub-results for the bilinear configs and the
     Wikidata5M-scale block, each with its own roofline; value, ms_per_step and the workload size agree."""
@@ -265,7 +265,7 @@ def test_bench_line_keeps_the_contract(tmp_path):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--details",
+    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--details",
                           str(tmp_path / "details.json")], capture_output=True, text=True, timeout=1500, cwd=root)
     assert run.returncode == 0, run.stderr[-2000:]
     lines = [l for l in run.stdout.splitlines() if l.strip()]
@@ -386,6 +386,41 @@ def test_bench_line_keeps_the_contract(tmp_path):
     dp = ib["dataparallel_two_replicas"]
     assert dp["replicas"] == 2 and 0 < dp["fused_us_per_step"] < dp["stock_us_per_step"]
     assert 0 < dp["fused_one_replica_alone_us"] < dp["stock_one_replica_alone_us"]
+
+
+@pytest.mark.default_routing
+def test_bench_plain_run_times_its_steps_and_dumps_what_they_computed(tmp_path):
+    """`python bench.py --steps K --warmup W` without --full: the headline only -- ONE line with the contract's keys, K timed
+    steps, none of the --full sections; --dump-outputs DIR writes the last timed step's counts and metric sums as float64, and
+    a second run with the same workload writes the same arrays (seeded inputs)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = []
+    for steps, out in ((4, "a"), (2, "b")):
+        run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", "1",
+                              "--dump-outputs", str(tmp_path / out)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert run.returncode == 0, run.stderr[-2000:]
+        got = [l for l in run.stdout.splitlines() if l.strip()]
+        assert len(got) == 1, got
+        lines.append(json.loads(got[0]))
+    line = lines[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "mrr", "mrr_filtered"):
+        assert key in line, key
+    for key in ("roofline", "cpu_baseline", "parity_check", "sub_results", "inbatch_loss", "hbm_probe", "details"):
+        assert key not in line, key
+    assert line["steps"] == 4 and lines[1]["steps"] == 2 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["metric"].startswith("scored triples/sec") and line["unit"] == "scored triples/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["config"]["workload"] == "fb15k237-transe"
+    assert line["value"] == pytest.approx(2 * 52870 * 14541 / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    counts, sums = np.load(tmp_path / "a" / "counts.npy"), np.load(tmp_path / "a" / "metric_sums.npy")
+    assert counts.dtype == np.float64 and counts.shape == (2 * 52870, 4) and sums.dtype == np.float64 and sums.shape == (8,)
+    assert np.array_equal(counts, np.round(counts)) and counts.min() >= 0 and counts.max() <= 14541
+    # (the line carries 6 significant figures)
+    assert sums[0] / (2 * 52870) == pytest.approx(line["mrr"], rel=1e-5) and sums[1] / (2 * 52870) == pytest.approx(line["mrr_filtered"], rel=1e-5)
+    assert np.array_equal(counts, np.load(tmp_path / "b" / "counts.npy")) and np.array_equal(sums, np.load(tmp_path / "b" / "metric_sums.npy"))
 
 
 @pytest.mark.parametrize("rel_model,D", [("transe", 300), ("transe", 768), ("distmult", 96), ("complex", 192),

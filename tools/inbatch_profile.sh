@@ -1,9 +1,9 @@
 #!/bin/bash
 # Per-kernel times of the in-batch loss step (forward + backward launches) under rocprofv3 (kernel trace + stats only), one
-# run per shape of bench.INBATCH_SHAPES:   bash tools/inbatch_profile.sh [out-dir under gpurun_out/]
+# run per shape of bench.INBATCH_SHAPES:   bash tools/inbatch_profile.sh [out-dir under $PROFILE_OUT, default profile_out/]
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=$(realpath -m "${PROFILE_OUT:-$R/profile_out}")/${1:-inbatch}
 cd /tmp && export TMPDIR=/tmp
-R=${GRAFT_REPO_ROOT:-/root/repo}
-OUT=$R/gpurun_out/${1:-inbatch}
 mkdir -p $OUT
 cd $R
 for S in inbatch-fb15k237 inbatch-wikidata5m-complex-fp16 inbatch-wikidata5m-complex-fp16-b1024; do
