@@ -26,7 +26,7 @@ SYMBOLS = ("blp_version", "blp_last_error", "blp_device_caps", "blp_selftest", "
            "blp_rank_all_batches_native16", "blp_profile_next_rank_kernel", "blp_rank_all_prepass_stats", "blp_rank_from_scores",
            "blp_rank_metrics", "blp_rank_metric_sums", "blp_score_fwd", "blp_score_bwd", "blp_inbatch_loss_save_floats",
            "blp_inbatch_loss_fwd_launches", "blp_inbatch_loss_fwd", "blp_inbatch_loss_bwd", "blp_project_rows_supported", "blp_project_rows", "blp_bow_rows_supported", "blp_bow_rows", "blp_dkrl_rows_supported", "blp_dkrl_rows",
-           "blp_build_queries")
+           "blp_build_queries", "blp_topk_supported", "blp_topk_workspace_bytes", "blp_topk", "blp_topk_merge")
 HOOK_SYMBOLS = ("blp_debug_set_knob", "blp_debug_gemm_dump", "blp_debug_reset_selftest")  # libblp_hip.hooks.so only
 KNOBS = ("rank_kernel", "gemm_kernel", "sad_queries_per_group", "sad_pass_groups", "sad_min_queries",
          "gemm_pass_words", "gemm_tiles_per_chunk", "exact_query_chunk",
@@ -186,6 +186,15 @@ def _load(path, hooks):
     L.blp_dkrl_rows_supported.argtypes = [_i, _i, _i]
     L.blp_dkrl_rows.restype = _i
     L.blp_dkrl_rows.argtypes = [_vp, _vp, _i64, _i, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _vp, _i, _vp]
+    L.blp_topk_supported.restype = _i
+    L.blp_topk_supported.argtypes = [_i, _i, _i]
+    L.blp_topk_workspace_bytes.restype = _sz
+    L.blp_topk_workspace_bytes.argtypes = [_i, _i64, _i, _i64, _i64, _i]
+    L.blp_topk.restype = _i
+    L.blp_topk.argtypes = [_i, _vp, _i64, _i, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i,
+                           ctypes.POINTER(BlpFilter), _vp, _vp, _vp, _sz, _i, _vp]
+    L.blp_topk_merge.restype = _i
+    L.blp_topk_merge.argtypes = [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _vp]
     if hooks:
         L.blp_debug_gemm_dump.restype = _i
         L.blp_debug_gemm_dump.argtypes = [_vp, _vp]

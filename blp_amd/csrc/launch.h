@@ -84,6 +84,19 @@ hipError_t launch_rank_all_batches16(int model, int D, const void* table, int dt
                                      int32_t* counts, void* workspace, int n_cu, hipStream_t stream, hipEvent_t ev_start = nullptr,
                                      hipEvent_t ev_stop = nullptr);
 
+// rank_all.hip: prep_coef_kernel's coefficient rows alone (C floats per query, Scorer<MODEL, SIDE, D>::C)
+hipError_t launch_prep_coef(int model, int D, const QRows q_fixed, const QRows q_rel, int64_t q_head, int64_t q_tail,
+                            float* coef_head, float* coef_tail, hipStream_t stream);
+
+// topk.hip: filtered top-k over the candidate table (include/blp_hip.h: blp_topk, blp_topk_merge)
+bool topk_supported(int model, int D, int k);
+size_t topk_workspace_bytes(int model, int D, int64_t N, int64_t q_head, int64_t q_tail, int k);
+hipError_t launch_topk(int model, int D, const float* table, int64_t N, int64_t ld, int64_t row_base, const QRows q_fixed,
+                       const QRows q_rel, int64_t q_head, int64_t q_tail, int k, const FilterSpec& filter, int64_t* rows,
+                       float* scores, void* workspace, hipStream_t stream);
+hipError_t launch_topk_merge(const int64_t* rows, const float* scores, int64_t Q, int64_t n_in, int k, int64_t* rows_out,
+                             float* scores_out, hipStream_t stream);
+
 hipError_t launch_rank_metrics(const int32_t* counts, int64_t Q, const int32_t* k, float* rr,
                                uint8_t* hits, hipStream_t stream);
 

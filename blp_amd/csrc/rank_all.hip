@@ -223,6 +223,29 @@ static void launch_true_key(const QRows q_true, const QRows& q_fixed,
     }
 }
 
+// The coefficient rows of prep_coef_kernel alone (blp_topk: topk.hip scores through them)
+template <int MODEL, int D>
+static hipError_t prep_coef_only(const QRows& q_fixed, const QRows& q_rel, int64_t q_head, int64_t q_tail, float* coef_head,
+                                 float* coef_tail, hipStream_t stream) {
+    const int64_t n = q_head * Scorer<MODEL, HEAD, D>::C + q_tail * Scorer<MODEL, TAIL, D>::C;
+    if (n == 0) return hipSuccess;
+    const int64_t blocks = (n + 255) / 256;
+    prep_coef_kernel<MODEL, D><<<(int)(blocks < 8192 ? blocks : 8192), 256, 0, stream>>>(q_fixed, q_rel, q_head, q_tail,
+                                                                                         coef_head, coef_tail);
+    return hipGetLastError();
+}
+
+hipError_t launch_prep_coef(int model, int D, const QRows q_fixed, const QRows q_rel, int64_t q_head, int64_t q_tail,
+                            float* coef_head, float* coef_tail, hipStream_t stream) {
+#define BLP_PREP_CASE(M, DD) \
+    if (model == M && D == DD) return prep_coef_only<M, DD>(q_fixed, q_rel, q_head, q_tail, coef_head, coef_tail, stream);
+#define BLP_PREP_MODEL(M) BLP_PREP_CASE(M, 64) BLP_PREP_CASE(M, 128) BLP_PREP_CASE(M, 256)
+    BLP_PREP_MODEL(TRANSE) BLP_PREP_MODEL(DISTMULT) BLP_PREP_MODEL(COMPLEX) BLP_PREP_MODEL(SIMPLE)
+#undef BLP_PREP_MODEL
+#undef BLP_PREP_CASE
+    return hipErrorInvalidValue;
+}
+
 // Stage `count` floats (a multiple of 4, at most 2 * 4 * 256) from global memory into LDS with
 // LDS-DMA (global_load_lds_dwordx4: 16 B per lane straight into LDS at wave-uniform base + lane * 16,
 // no VGPR round trip).  The copy stays in flight until the caller's `s_waitcnt vmcnt(0)` + barrier.

@@ -1,0 +1,367 @@
+// topk.hip -- filtered, deterministic top-k entity prediction over the whole candidate table (include/blp_hip.h:
+// blp_topk, blp_topk_merge): for a query (h, r, ?) / (?, r, t) the k rows with the highest score_fn value
+// (models.py:222-248), without materialising the (Q, N) score matrix.
+//
+// Order.  Every (candidate, query) pair becomes one 64-bit KEY, larger = better:
+//   high word  the score made orderable as an unsigned integer (IEEE order; -0 and +0 equal; every NaN = 1, below -inf);
+//   low word   (0x7fffffff - row) << 1 | (score is -0): among equal scores the smaller row wins; the bit only carries
+//              the sign of zero (rows are distinct, so it never decides);
+//   key 0      an empty slot (row -1, score NaN): it sorts after everything.
+// The top k of a query are the k largest keys -- a set that does not depend on the order the keys are seen in, so the
+// result is deterministic whatever the grid.
+//
+// Kernels of one blp_topk call (all on the caller's stream):
+//   1. prep_coef    (rank_all.hip) the queries' coefficient rows, as for the exact ranking kernels
+//   2. topk_tiles   rank_tiles' layout: a wave owns a tile of 64 table rows, one row per lane in D VGPRs, and applies every
+//                   query of its workgroup's chunk to it (Scorer<> arithmetic, coefficients as SGPR operands).  Per (wave,
+//                   query) an LDS list holds the best k keys seen so far, sorted; its last entry is the admission threshold.
+//                   A tile costs a query two compares and a ballot once the list is warm: only lanes above the threshold are
+//                   checked against the query's filter segment (filter_row, as filter_finalize walks it) and inserted, one
+//                   key at a time (each lane moves its slots of the list by one).  At the end the workgroup folds its four
+//                   waves' lists into one and writes it to the workspace: (Q, n_slabs, k) keys.
+//   3. topk_merge   one workgroup per query selects the k best of its n_slabs lists the same way and writes rows / scores.
+//                   blp_topk_merge is this kernel on caller-given (rows, scores) lists.
+//   4. topk_rescore the k rows of every query re-scored with the reference's literal "0 + first term" additions
+//                   (Scorer<>::score<true>, = blp_score_fwd's arithmetic): the keys compare -0 and +0 as equal, the output
+//                   carries the reference's sign of zero.
+// Grid of topk_tiles: (query chunk x candidate slab), bounded: few queries against a long table -> one chunk, up to
+// kTopkTargetGroups slabs grid-striding over the tiles (HBM-bound); many queries -> one slab per chunk, the table re-read from
+// L2 by every chunk (VALU-bound).  Nothing is dynamically indexed in registers: lists live in LDS.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "launch.h"
+#include "rank_common.h"
+#include "score_core.h"
+#include "tile.h"
+
+#pragma clang fp contract(off)
+
+namespace blp {
+
+typedef unsigned long long u64;
+
+constexpr int kTopkWaves = 4;               // waves per workgroup of topk_tiles
+constexpr int kTopkMaxChunk = 32;           // queries per workgroup
+constexpr int kTopkListBytes = 24576;       // LDS for the lists of one workgroup (kTopkWaves x chunk x k keys)
+constexpr int kTopkTargetGroups = 512;      // workgroups of topk_tiles when the queries alone give fewer
+constexpr int kTopkMaxK = 256;
+constexpr int kTopkMergeMaxWaves = 16;
+
+__host__ __device__ inline int topk_chunk(int k) {
+    const int c = kTopkListBytes / (kTopkWaves * 8 * k);
+    return c < 1 ? 1 : (c > kTopkMaxChunk ? kTopkMaxChunk : c);
+}
+
+// candidate slabs per query chunk: n_slabs x n_chunks <= max(n_chunks, kTopkTargetGroups), and at most one per kTopkWaves tiles
+static int64_t topk_slabs(int64_t N, int64_t Q, int k) {
+    const int64_t chunks = (Q + topk_chunk(k) - 1) / topk_chunk(k);
+    const int64_t tiles = (N + kTileRows - 1) / kTileRows;
+    int64_t s = chunks > 0 ? kTopkTargetGroups / chunks : 1;
+    const int64_t cap = (tiles + kTopkWaves - 1) / kTopkWaves;
+    if (s > cap) s = cap;
+    return s < 1 ? 1 : s;
+}
+
+__device__ __forceinline__ u64 topk_key(float s, int64_t row) {
+    unsigned b = __float_as_uint(s);
+    const unsigned neg0 = b == 0x80000000u;
+    unsigned hi;
+    if (__builtin_isnan(s)) {
+        hi = 1u;
+    } else {
+        if (neg0) b = 0u;
+        hi = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    }
+    const unsigned lo = ((0x7fffffffu - (unsigned)row) << 1) | neg0;
+    return ((u64)hi << 32) | lo;
+}
+__device__ __forceinline__ int64_t key_row(u64 key) { return key ? (int64_t)(0x7fffffffu - ((unsigned)key >> 1)) : -1; }
+__device__ __forceinline__ float key_score(u64 key) {
+    const unsigned hi = (unsigned)(key >> 32);
+    if (hi <= 1u) return __uint_as_float(0x7fc00000u);
+    unsigned b = (hi & 0x80000000u) ? (hi & 0x7fffffffu) : ~hi;
+    if (key & 1ull) b = 0x80000000u;
+    return __uint_as_float(b);
+}
+
+// Insert x (wave-uniform) into the list L[0, n) in LDS, sorted descending, dropping its last entry.  Lane l moves slots
+// l, l + 64, ... (n <= kTopkMaxK: four per lane, statically indexed).
+__device__ __forceinline__ void list_insert(u64* L, int n, u64 x, int lane) {
+    u64 nv[kTopkMaxK / 64];
+    static_for<kTopkMaxK / 64>([&](auto jj) {
+        constexpr int j = decltype(jj)::value;
+        const int p = lane + 64 * j;
+        if (p < n) {
+            const u64 old = L[p];
+            const u64 prev = p > 0 ? L[p - 1] : ~0ull;
+            nv[j] = old > x ? old : (prev > x ? x : prev);
+        }
+    });
+    wave_lds_sync();
+    static_for<kTopkMaxK / 64>([&](auto jj) {
+        constexpr int j = decltype(jj)::value;
+        const int p = lane + 64 * j;
+        if (p < n) L[p] = nv[j];
+    });
+    wave_lds_sync();
+}
+
+// Offer the wave's 64 keys (one per lane; 0 = none) to the list L[0, n): lanes above its last entry, minus those
+// drop(mask) removes, are inserted.
+template <class Drop>
+__device__ __forceinline__ void list_offer(u64* L, int n, u64 key, int lane, Drop drop) {
+    u64 thr = L[n - 1];
+    u64 mask = __ballot(key > thr);
+    if (!mask) return;
+    mask = drop(mask);
+    while (mask) {
+        const int b = __builtin_ctzll(mask);
+        mask &= mask - 1;
+        const u64 x = __shfl(key, b);
+        if (x <= thr) continue;
+        list_insert(L, n, x, lane);
+        thr = L[n - 1];
+    }
+}
+
+// The lanes of `mask` whose candidate (table row row0 + lane) query q's filter segment does NOT remove: the segment is
+// read 64 entries at a time (filter_row: exclude, ent2idx, row_base as filter_finalize applies them), every candidate of
+// the mask looked up with one compare + ballot per chunk.
+__device__ __forceinline__ u64 unfiltered(const FilterSpec& f, int64_t q, int64_t N, int64_t row0, u64 mask, int lane) {
+    const int64_t lo = f.lo[q], hi = f.hi[q];
+    for (int64_t c = lo; c < hi && mask; c += 64) {
+        const int64_t v = c + lane < hi ? filter_row(f, q, c + lane, N) : -1;
+        u64 m = mask;
+        while (m) {
+            const int b = __builtin_ctzll(m);
+            m &= m - 1;
+            if (__ballot(v == row0 + b)) mask &= ~(1ull << b);
+        }
+    }
+    return mask;
+}
+
+// queries [q_lo, q_hi) of one side against the wave's tile; coef = the coefficient row of q_lo
+template <int MODEL, int SIDE, int D>
+__device__ __forceinline__ void topk_side(const float (&e)[D], bool valid, int64_t row0, int64_t row_base, int64_t N,
+                                          const float* __restrict__ coef, int64_t q_lo, int64_t q_hi, int64_t qa, u64* lists,
+                                          int k, const FilterSpec& f, int lane) {
+    using S = Scorer<MODEL, SIDE, D>;
+    for (int64_t q = q_lo; q < q_hi; ++q) {
+        const float s = S::template score<false>(e, PtrCoef{coef + (q - q_lo) * S::C});
+        const u64 key = valid ? topk_key(s, row_base + row0 + lane) : 0ull;
+        list_offer(lists + (q - qa) * k, k, key, lane,
+                   [&](u64 m) { return f.on() ? unfiltered(f, q, N, row0, m, lane) : m; });
+    }
+}
+
+template <int MODEL, int D>
+__global__ __launch_bounds__(kTopkWaves * 64, (D == 256 ? 1 : 2)) void topk_tiles_kernel(
+    const float* __restrict__ table, int64_t N, int64_t ld, int64_t row_base, const float* __restrict__ coef_head,
+    const float* __restrict__ coef_tail, int64_t q_head, int64_t q_tail, int q_chunk, int n_slabs, int k,
+    const FilterSpec filter, u64* __restrict__ partial) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63;
+    float* slab = smem + wave * kSlabFloats;
+    u64* lists_all = reinterpret_cast<u64*>(smem + kTopkWaves * kSlabFloats);
+    u64* lists = lists_all + (size_t)wave * q_chunk * k;
+
+    const int64_t chunk = blockIdx.x / n_slabs;
+    const int s = blockIdx.x % n_slabs;
+    const int64_t Q = q_head + q_tail;
+    const int64_t qa = chunk * q_chunk, qb = qa + q_chunk < Q ? qa + q_chunk : Q;
+    const int nq = (int)(qb - qa);
+    const int64_t h_lo = qa < q_head ? qa : q_head, h_hi = qb < q_head ? qb : q_head;
+    const int64_t t_lo = qa > q_head ? qa : q_head, t_hi = qb > q_head ? qb : q_head;
+    const float* ch = coef_head + h_lo * Scorer<MODEL, HEAD, D>::C;
+    const float* ct = coef_tail + (t_lo - q_head) * Scorer<MODEL, TAIL, D>::C;
+
+    for (int i = lane; i < nq * k; i += 64) lists[i] = 0ull;
+    wave_lds_sync();
+
+    const int64_t n_tiles = (N + kTileRows - 1) / kTileRows;
+    for (int64_t t = (int64_t)s * kTopkWaves + wave; t < n_tiles; t += (int64_t)n_slabs * kTopkWaves) {
+        float e[D];
+        const int64_t row0 = t * kTileRows;
+        load_tile<D, false>(e, table, N, ld, row0, slab, lane);  // rows past the end are clamped, then masked
+        const bool valid = row0 + lane < N;
+        topk_side<MODEL, HEAD, D>(e, valid, row0, row_base, N, ch, h_lo, h_hi, qa, lists, k, filter, lane);
+        topk_side<MODEL, TAIL, D>(e, valid, row0, row_base, N, ct, t_lo, t_hi, qa, lists, k, filter, lane);
+    }
+
+    __syncthreads();
+    // fold the other waves' lists into wave 0's, query j by wave j % kTopkWaves; write the workgroup's list
+    for (int j = wave; j < nq; j += kTopkWaves) {
+        u64* L = lists_all + (size_t)j * k;
+        for (int w = 1; w < kTopkWaves; ++w) {
+            const u64* src = lists_all + ((size_t)w * q_chunk + j) * k;
+            for (int c = 0; c < k; c += 64)
+                list_offer(L, k, c + lane < k ? src[c + lane] : 0ull, lane, [](u64 m) { return m; });
+        }
+        u64* out = partial + ((size_t)(qa + j) * n_slabs + s) * k;
+        for (int i = lane; i < k; i += 64) out[i] = L[i];
+    }
+}
+
+// One workgroup (blockDim.x / 64 waves) per query: the k best of its n_in keys -- `keys` (Q, n_in), or made from
+// (rows, scores) (Q, n_in), a row < 0 being an empty slot.  Wave w takes entries w x 64 ..., the next chunk's load
+// issued before the current one is offered; wave 0 folds the others' lists into its own and writes the result.
+template <bool FROM_KEYS>
+__global__ __launch_bounds__(kTopkMergeMaxWaves * 64) void topk_merge_kernel(const u64* __restrict__ keys,
+                                                                             const int64_t* __restrict__ rows_in,
+                                                                             const float* __restrict__ scores_in, int64_t n_in,
+                                                                             int k, int64_t* __restrict__ rows_out,
+                                                                             float* __restrict__ scores_out) {
+    extern __shared__ u64 mlists[];
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63;
+    const int waves = blockDim.x / 64;
+    const int64_t q = blockIdx.x;
+    u64* L = mlists + (size_t)wave * k;
+    for (int i = lane; i < k; i += 64) L[i] = 0ull;
+    wave_lds_sync();
+
+    auto fetch = [&](int64_t i) -> u64 {
+        if (i >= n_in) return 0ull;
+        if constexpr (FROM_KEYS) {
+            return keys[q * n_in + i];
+        } else {
+            const int64_t r = rows_in[q * n_in + i];
+            return r < 0 ? 0ull : topk_key(scores_in[q * n_in + i], r);
+        }
+    };
+    const int64_t stride = (int64_t)waves * 64;
+    u64 cur = fetch((int64_t)wave * 64 + lane);
+    for (int64_t c = (int64_t)wave * 64; c < n_in; c += stride) {
+        const u64 nxt = fetch(c + stride + lane);
+        list_offer(L, k, cur, lane, [](u64 m) { return m; });
+        cur = nxt;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        for (int w = 1; w < waves; ++w)
+            for (int c = 0; c < k; c += 64)
+                list_offer(L, k, c + lane < k ? mlists[(size_t)w * k + c + lane] : 0ull, lane, [](u64 m) { return m; });
+        for (int i = lane; i < k; i += 64) {
+            const u64 key = L[i];
+            rows_out[q * k + i] = key_row(key);
+            scores_out[q * k + i] = key_score(key);
+        }
+    }
+}
+
+// One lane per output slot: the score of the selected row by Scorer<>::score<true> from the query's own vectors
+// (LazyCoef) -- blp_score_fwd's arithmetic, bit for bit, sign of zero included.  Empty slots keep NaN.
+template <int MODEL, int D>
+__global__ __launch_bounds__(64) void topk_rescore_kernel(const float* __restrict__ table, int64_t ld, int64_t row_base,
+                                                          const QRows q_fixed, const QRows q_rel, int64_t q_head, int64_t Q,
+                                                          int k, const int64_t* __restrict__ rows, float* __restrict__ scores) {
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= Q * k) return;
+    const int64_t r = rows[i];
+    if (r < 0) return;
+    const int64_t q = i / k;
+    float e[D];
+    load_row<D>(e, table + (r - row_base) * ld);
+    const float* f = q_fixed.row(q);
+    const float* rel = q_rel.row(q);
+    float s;
+    if (q < q_head)
+        s = Scorer<MODEL, HEAD, D>::template score<true>(e, LazyCoef<MODEL, HEAD, D>{f, rel});
+    else
+        s = Scorer<MODEL, TAIL, D>::template score<true>(e, LazyCoef<MODEL, TAIL, D>{f, rel});
+    scores[i] = s;
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+bool topk_supported(int model, int D, int k) {
+    return model >= TRANSE && model <= SIMPLE && (D == 64 || D == 128 || D == 256) && k >= 1 && k <= kTopkMaxK;
+}
+
+struct TopkWorkspace {
+    float* coef_head;
+    float* coef_tail;
+    u64* partial;
+    size_t bytes;
+};
+
+static TopkWorkspace carve_topk(void* base, int D, int64_t N, int64_t q_head, int64_t q_tail, int k) {
+    const int64_t Q = q_head + q_tail;
+    const size_t coef_h = align_up((size_t)q_head * max_coef(D) * 4, 256), coef_t = align_up((size_t)q_tail * max_coef(D) * 4, 256);
+    const size_t part = align_up((size_t)Q * topk_slabs(N, Q, k) * k * 8, 256);
+    char* p = static_cast<char*>(base);
+    TopkWorkspace w;
+    w.coef_head = reinterpret_cast<float*>(p);
+    w.coef_tail = reinterpret_cast<float*>(p + coef_h);
+    w.partial = reinterpret_cast<u64*>(p + coef_h + coef_t);
+    w.bytes = coef_h + coef_t + part;
+    return w;
+}
+
+size_t topk_workspace_bytes(int model, int D, int64_t N, int64_t q_head, int64_t q_tail, int k) {
+    if (!topk_supported(model, D, k) || N < 0 || q_head < 0 || q_tail < 0) return 0;
+    return carve_topk(nullptr, D, N, q_head, q_tail, k).bytes;
+}
+
+static hipError_t launch_merge(const u64* keys, const int64_t* rows_in, const float* scores_in, int64_t Q, int64_t n_in, int k,
+                               int64_t* rows_out, float* scores_out, hipStream_t stream) {
+    if (Q == 0) return hipSuccess;
+    int64_t waves = n_in / 256;  // a wave per >= 4 chunks of 64 entries
+    waves = waves < 1 ? 1 : (waves > kTopkMergeMaxWaves ? kTopkMergeMaxWaves : waves);
+    const size_t lds = (size_t)waves * k * 8;
+    if (keys)
+        topk_merge_kernel<true><<<dim3((unsigned)Q), (unsigned)(waves * 64), lds, stream>>>(keys, nullptr, nullptr, n_in, k,
+                                                                                           rows_out, scores_out);
+    else
+        topk_merge_kernel<false><<<dim3((unsigned)Q), (unsigned)(waves * 64), lds, stream>>>(nullptr, rows_in, scores_in, n_in,
+                                                                                            k, rows_out, scores_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_topk_merge(const int64_t* rows, const float* scores, int64_t Q, int64_t n_in, int k, int64_t* rows_out,
+                             float* scores_out, hipStream_t stream) {
+    return launch_merge(nullptr, rows, scores, Q, n_in, k, rows_out, scores_out, stream);
+}
+
+template <int MODEL, int D>
+static hipError_t topk_impl(const float* table, int64_t N, int64_t ld, int64_t row_base, const QRows& q_fixed, const QRows& q_rel,
+                            int64_t q_head, int64_t q_tail, int k, const FilterSpec& filter, int64_t* rows, float* scores,
+                            void* workspace, hipStream_t stream) {
+    const int64_t Q = q_head + q_tail;
+    if (Q == 0) return hipSuccess;
+    if (N == 0) return launch_merge(nullptr, rows, scores, Q, 0, k, rows, scores, stream);  // every slot empty
+    const TopkWorkspace w = carve_topk(workspace, D, N, q_head, q_tail, k);
+    hipError_t err = launch_prep_coef(MODEL, D, q_fixed, q_rel, q_head, q_tail, w.coef_head, w.coef_tail, stream);
+    if (err != hipSuccess) return err;
+    const int q_chunk = topk_chunk(k);
+    const int64_t n_slabs = topk_slabs(N, Q, k), n_chunks = (Q + q_chunk - 1) / q_chunk;
+    const size_t lds = (size_t)kTopkWaves * kSlabFloats * 4 + (size_t)kTopkWaves * q_chunk * k * 8;
+    topk_tiles_kernel<MODEL, D><<<dim3((unsigned)(n_chunks * n_slabs)), kTopkWaves * 64, lds, stream>>>(
+        table, N, ld, row_base, w.coef_head, w.coef_tail, q_head, q_tail, q_chunk, (int)n_slabs, k, filter, w.partial);
+    if ((err = hipGetLastError()) != hipSuccess) return err;
+    if ((err = launch_merge(w.partial, nullptr, nullptr, Q, n_slabs * k, k, rows, scores, stream)) != hipSuccess) return err;
+    const int64_t slots = Q * k;
+    topk_rescore_kernel<MODEL, D><<<dim3((unsigned)((slots + 63) / 64)), 64, 0, stream>>>(table, ld, row_base, q_fixed, q_rel,
+                                                                                          q_head, Q, k, rows, scores);
+    return hipGetLastError();
+}
+
+hipError_t launch_topk(int model, int D, const float* table, int64_t N, int64_t ld, int64_t row_base, const QRows q_fixed,
+                       const QRows q_rel, int64_t q_head, int64_t q_tail, int k, const FilterSpec& filter, int64_t* rows,
+                       float* scores, void* workspace, hipStream_t stream) {
+#define BLP_TOPK_CASE(M, DD)                                                                                              \
+    if (model == M && D == DD)                                                                                            \
+        return topk_impl<M, DD>(table, N, ld, row_base, q_fixed, q_rel, q_head, q_tail, k, filter, rows, scores, workspace, \
+                                stream);
+#define BLP_TOPK_MODEL(M) BLP_TOPK_CASE(M, 64) BLP_TOPK_CASE(M, 128) BLP_TOPK_CASE(M, 256)
+    BLP_TOPK_MODEL(TRANSE) BLP_TOPK_MODEL(DISTMULT) BLP_TOPK_MODEL(COMPLEX) BLP_TOPK_MODEL(SIMPLE)
+#undef BLP_TOPK_MODEL
+#undef BLP_TOPK_CASE
+    return hipErrorInvalidValue;
+}
+
+}  // namespace blp

@@ -3,6 +3,7 @@ device memory and the stream; every arithmetic step of the hot path runs in the 
 
     rank_all(...)       all-entities ranking counts        (train.py:146-171, utils.py:103-105)
     rank_metrics(...)   counts -> reciprocal ranks, hits   (utils.py:104-109)
+    topk(...)           filtered top-k prediction per query (no score matrix)
     score(...)          score_fn(heads, tails, rels)       (models.py:222-248), differentiable
     inbatch_loss(...)   compute_loss on in-batch negatives (models.py:51-70), differentiable
 
@@ -340,6 +341,89 @@ def rank_all_shard(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head
     if status:
         _lib.check(status, "blp_rank_all_shard")
     return counts
+
+
+def topk_supported(rel_model, dim, k):
+    """True if topk takes this width and k (include/blp_hip.h: blp_topk_supported -- D in {64, 128, 256}, 1 <= k <= 256)."""
+    return bool(_lib.lib().blp_topk_supported(_lib.MODEL_IDS[rel_model], int(dim), int(k)))
+
+
+def topk_workspace_bytes(rel_model, N, D, q_head, q_tail, k):
+    return int(_lib.lib().blp_topk_workspace_bytes(_lib.MODEL_IDS[rel_model], int(N), int(D), int(q_head), int(q_tail), int(k)))
+
+
+def topk(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, filter=None, row_base=0, out=None):
+    """Filtered top-k prediction (blp_topk): for each query -- head-replacing [0, q_head), then tail-replacing; fixed entity
+    row fixed_row[q] of ``source`` (S, D), relation row rel_ids[q] of ``rel_emb`` (R, D) -- the k rows of ``table`` (N, D),
+    global rows [row_base, row_base + N), with the highest score_fn value, as blp_topk orders them (descending score, ties by
+    ascending row, NaN last; numpy's argsort(-scores, kind="stable")[:k]).  ``filter``: a SegmentFilter whose row_base is
+    ``row_base``; the rows it names are removed.  Slots beyond the candidates left: row -1, score NaN.
+    Returns (rows (Q, k) int64, scores (Q, k) float32); ``out`` may give both."""
+    _require_device(table, source, fixed_row, rel_emb, rel_ids)
+    table = _f32_rows(table, "table")
+    source = table if source is table else _f32_rows(source, "source")
+    rel_emb = _f32_rows(rel_emb, "rel_emb").contiguous()
+    N, D = table.shape
+    if source.dim() != 2 or source.shape[1] != D:
+        raise ValueError(f"source must be (S, {D}), got {tuple(source.shape)}")
+    fixed_row, rel_ids = _i64_vector(fixed_row), _i64_vector(rel_ids)
+    Q = fixed_row.shape[0]
+    k = int(k)
+    if rel_ids.shape[0] != Q or rel_emb.dim() != 2 or rel_emb.shape[1] != D:
+        raise ValueError("fixed_row and rel_ids need one entry per query; rel_emb must be (R, D)")
+    if not 0 <= q_head <= Q:
+        raise ValueError(f"q_head = {q_head} outside [0, {Q}]")
+    if not topk_supported(rel_model, D, k):
+        raise ValueError(f"topk: D = {D}, k = {k} not supported (D in 64 / 128 / 256, 1 <= k <= 256): see topk_supported")
+    if filter is not None and int(filter.row_base) != int(row_base):
+        raise ValueError(f"topk: the filter's row_base {filter.row_base} differs from row_base {row_base}")
+    dev = table.device
+    if out is None:
+        out = (torch.empty((Q, k), dtype=torch.int64, device=dev), torch.empty((Q, k), dtype=torch.float32, device=dev))
+    rows, scores = out
+    if rows.shape != (Q, k) or rows.dtype != torch.int64 or not rows.is_contiguous() or scores.shape != (Q, k) or \
+            scores.dtype != torch.float32 or not scores.is_contiguous():
+        raise ValueError("out must be contiguous (Q, k) int64 rows and (Q, k) float32 scores")
+    if Q == 0:
+        return rows, scores
+    L = _lib.lib()
+    model = _lib.MODEL_IDS[rel_model]
+    ws_bytes = L.blp_topk_workspace_bytes(model, N, D, q_head, Q - q_head, k)
+    stream = torch._C._cuda_getCurrentRawStream(dev.index)
+    workspace = _workspace(dev, stream, ws_bytes)
+    spec = None if filter is None else _filter_spec(filter, Q, dev)
+    status = L.blp_topk(model, table.data_ptr(), N, D, table.stride(0) if N > 1 else D, int(row_base), source.data_ptr(),
+                        source.shape[0], source.stride(0) if source.shape[0] > 1 else D, fixed_row.data_ptr(), rel_emb.data_ptr(),
+                        rel_emb.shape[0], rel_ids.data_ptr(), q_head, Q - q_head, k, spec, rows.data_ptr(), scores.data_ptr(),
+                        workspace.data_ptr(), ws_bytes, dev.index, stream)
+    if status:
+        _lib.check(status, "blp_topk")
+    return rows, scores
+
+
+def topk_merge(rows, scores, k):
+    """The k best of per-query candidate lists (blp_topk_merge): rows (Q, n) int64 global rows (< 0: an empty slot) and
+    scores (Q, n) float32 -- e.g. the topk results of several candidate shards side by side -- in topk's order.
+    Returns (rows (Q, k), scores (Q, k))."""
+    _require_device(rows, scores)
+    if rows.dim() != 2 or scores.shape != rows.shape:
+        raise ValueError("rows and scores must be (Q, n) of the same shape")
+    rows = rows.to(torch.int64).contiguous()
+    scores = _f32_rows(scores, "scores").contiguous()
+    Q, n = rows.shape
+    k = int(k)
+    if not 1 <= k <= 256 or n < 1:
+        raise ValueError(f"topk_merge: k = {k} outside [1, 256] or empty lists")
+    dev = rows.device
+    rows_out = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    scores_out = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    if Q == 0:
+        return rows_out, scores_out
+    status = _lib.lib().blp_topk_merge(rows.data_ptr(), scores.data_ptr(), Q, 1, n, k, rows_out.data_ptr(), scores_out.data_ptr(),
+                                       dev.index, torch._C._cuda_getCurrentRawStream(dev.index))
+    if status:
+        _lib.check(status, "blp_topk_merge")
+    return rows_out, scores_out
 
 
 def rank_all_batches(rel_model, table, fixed_row, rel_emb, rel_ids, true_row, num_triples, batch, filter=None, out=None, source=None,

@@ -470,6 +470,145 @@ def rank_triples(model, table, triples, ent2idx, index=None, *, num_entities=Non
 
 
 # ----------------------------------------------------------------------------------- evaluation
+# ----------------------------------------------------------------------------------- link prediction (top-k)
+def _stable_topk(scores, rows, removed, k):
+    """Order of blp_topk on dense candidate lists: (Q, n) scores, global rows, removed flags -> the first k (rows, scores) by
+    descending score (-0 == +0), ties by ascending row, NaN after every number, removed entries and rows < 0 dropped; slots
+    beyond the candidates left: -1 / NaN.  numpy's argsort(-scores, kind="stable") for rows in ascending order."""
+    gone = removed | (rows < 0)
+    order = torch.argsort(torch.where(gone, torch.iinfo(torch.int64).max, rows), dim=1, stable=True)
+    neg = -scores.gather(1, order)
+    order = order.gather(1, torch.sort(neg, dim=1, stable=True).indices)
+    order = order.gather(1, torch.sort(gone.gather(1, order).to(torch.uint8), dim=1, stable=True).indices)
+    n = scores.shape[1]
+    take = order[:, :min(k, n)]
+    out_rows = torch.where(gone.gather(1, take), -1, rows.gather(1, take))
+    out_scores = torch.where(out_rows < 0, float("nan"), scores.gather(1, take))
+    if k > n:
+        pad = k - n
+        out_rows = torch.cat((out_rows, out_rows.new_full((out_rows.shape[0], pad), -1)), 1)
+        out_scores = torch.cat((out_scores, out_scores.new_full((out_scores.shape[0], pad), float("nan"))), 1)
+    return out_rows, out_scores
+
+
+def _topk_dense(score_fn, table, fixed, rel, q_head, k, row_base, filt, max_matrix_bytes=1 << 28):
+    """The reference's route (score_fn over the whole table, train.py:146-147) + the stable order, in query chunks of a
+    bounded (chunk, N) matrix: CPU tensors, and widths blp_topk is not compiled for.  filt: (seg_lo, seg_hi, values,
+    exclude, ent2idx) as SegmentFilter holds them, or None."""
+    Q, N = fixed.shape[0], table.shape[0]
+    dev = table.device
+    chunk = max(1, min(max(Q, 1), max_matrix_bytes // max(4 * N, 1)))
+    ent = table.unsqueeze(0)
+    grows = torch.arange(row_base, row_base + N, device=dev, dtype=torch.int64)
+    rows_out = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    scores_out = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    for lo in range(0, Q, chunk):
+        hi = min(lo + chunk, Q)
+        parts = []
+        for a, b, head in ((lo, min(hi, q_head), True), (max(lo, q_head), hi, False)):
+            if a < b:
+                f, r = fixed[a:b].unsqueeze(1), rel[a:b].unsqueeze(1)
+                parts.append(score_fn(ent, f, r) if head else score_fn(f, ent, r))
+        pred = torch.cat(parts) if len(parts) > 1 else parts[0]
+        removed = torch.zeros(pred.shape, dtype=torch.bool, device=dev)
+        if filt is not None:
+            seg_lo, seg_hi, values, exclude, e2i = filt
+            n_per = (seg_hi[lo:hi] - seg_lo[lo:hi]).clamp(min=0)
+            total = int(n_per.sum())
+            if total:
+                owner = torch.repeat_interleave(torch.arange(hi - lo, device=dev), n_per, output_size=total)
+                first = torch.cumsum(n_per, 0) - n_per
+                vals = values[seg_lo[lo:hi][owner] + torch.arange(total, device=dev) - first[owner]]
+                keep = torch.ones_like(vals, dtype=torch.bool) if exclude is None else vals != exclude[lo:hi][owner]
+                if e2i is not None:
+                    ok = (vals >= 0) & (vals < e2i.shape[0])
+                    vals = torch.where(ok, e2i[torch.where(ok, vals, torch.zeros_like(vals))], torch.full_like(vals, -1))
+                local = vals - row_base
+                keep &= (local >= 0) & (local < N)
+                removed[owner[keep], local[keep]] = True
+        rows_out[lo:hi], scores_out[lo:hi] = _stable_topk(pred, grows.expand(hi - lo, N), removed, k)
+    return rows_out, scores_out
+
+
+def predict_links(model, table, triples, k, ent2idx, *, side="both", filter_index=None, entities=None, group=None, world=1,
+                  rank=0, num_entities=None):
+    """Answer link-prediction queries: for every triple (head, tail, rel) of ``triples`` (T, 3) the k table rows the model
+    scores highest as the replaced entity -- ``side`` "head": (?, r, t); "tail": (h, r, ?); "both": [heads | tails], the
+    evaluation's order (train.py:149).  The entity at the replaced position is not used, except that a known edge never
+    filters the triple's own entity (utils.py:71,78): pass -1 there to have every known edge filtered.
+    table        (N, D) entity table (build_entity_table); with world > 1 this rank's rows shard_bounds(num_entities, world,
+                 rank) of it, and every rank calls with the same triples
+    ent2idx      utils.make_ent2idx map (entity id -> table row); the fixed entity of every query must have a row
+    filter_index utils.FilterIndex of the known edges (the training graph): the rows it names are removed, not demoted
+    entities     optional (num_entities,) entity id of every table row: ids instead of rows are returned
+    Returns (rows or ids (Q, k) int64, scores (Q, k) float32): descending score, ties by ascending row, NaN last; -1 / NaN
+    beyond the candidates left.  Scores are score_fn's values bit for bit.  HIP tensors at a width blp_topk takes: blp_topk
+    (one call per rank; shards merged by one all-gather of the (Q, k) lists + blp_topk_merge); otherwise the reference's
+    dense route (score_fn + a stable sort) in query chunks."""
+    model = _module(model)
+    if side not in ("head", "tail", "both"):
+        raise ValueError(f"side must be 'head', 'tail' or 'both', got {side!r}")
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"k = {k} must be >= 1")
+    device = table.device
+    n_local, D = table.shape
+    num_entities = n_local if num_entities is None else int(num_entities)
+    row_lo = shard_bounds(num_entities, world, rank)[0] if world > 1 else 0
+    triples = triples.to(device=device, dtype=torch.long).reshape(-1, 3)
+    ent2idx = ent2idx.to(device=device, dtype=torch.long)
+    T = triples.shape[0]
+    h, t, r = triples[:, 0], triples[:, 1], triples[:, 2]
+    heads, tails = side in ("head", "both"), side in ("tail", "both")
+    q_head = T if heads else 0
+    fixed_ids = torch.cat([x for x, on in ((t, heads), (h, tails)) if on])
+    rel_ids = torch.cat([r] * (int(heads) + int(tails)))
+    Q = fixed_ids.shape[0]
+    known = (fixed_ids >= 0) & (fixed_ids < ent2idx.shape[0])
+    fixed_rows = torch.where(known, ent2idx[torch.where(known, fixed_ids, torch.zeros_like(fixed_ids))], torch.full_like(fixed_ids, -1))
+    rel_w = model.rel_emb.weight.detach()
+    if Q and bool(((fixed_rows < 0) | (fixed_rows >= num_entities) | (rel_ids < 0) | (rel_ids >= rel_w.shape[0])).any()):
+        raise ValueError("predict_links: a query's fixed entity has no table row, or its relation is out of range")
+    # the vectors the queries are made of, on every rank: owner-filled, then summed over the ranks
+    if world > 1:
+        local = fixed_rows - row_lo
+        mine = (local >= 0) & (local < n_local)
+        fixed_vecs = torch.zeros((Q, D), dtype=table.dtype, device=device)
+        fixed_vecs[mine] = table[local[mine]]
+        _all_reduce(fixed_vecs, group)
+        source, src_rows = fixed_vecs, torch.arange(Q, device=device)
+    else:
+        source, src_rows = table, fixed_rows
+    filt = None
+    if filter_index is not None and Q:
+        seg = filter_index.segments(triples, ent2idx, device, row_base=row_lo)
+        sel = torch.cat([x for x, on in ((torch.arange(T, device=device), heads), (torch.arange(T, 2 * T, device=device), tails)) if on])
+        filt = ops.SegmentFilter(seg.seg_lo[sel].contiguous(), seg.seg_hi[sel].contiguous(), seg.values,
+                                 seg.exclude[sel].contiguous(), seg.ent2idx, row_lo)
+    fused = table.is_cuda and table.dtype == torch.float32 and ops.topk_supported(model.rel_model, D, k)
+    if fused:
+        rows, scores = ops.topk(model.rel_model, table, source, src_rows, rel_w, rel_ids, q_head, k, filter=filt, row_base=row_lo)
+    else:
+        dense_filt = None if filt is None else (filt.seg_lo, filt.seg_hi, filt.values, filt.exclude, filt.ent2idx)
+        rows, scores = _topk_dense(model.score_fn, table, source[src_rows], rel_w[rel_ids], q_head, k, row_lo, dense_filt)
+    if world > 1:
+        # ONE all-gather of every rank's (Q, k) list, rows and score bits packed together, then the merge
+        packed = torch.stack((rows, scores.view(torch.int32).to(torch.int64)), dim=-1)
+        full = torch.empty((world * Q, k, 2), dtype=packed.dtype, device=device)
+        _all_gather_into(full, packed, group)
+        full = full.view(world, Q, k, 2)
+        all_rows = full[..., 0].permute(1, 0, 2).reshape(Q, world * k)
+        all_scores = full[..., 1].to(torch.int32).view(torch.float32).permute(1, 0, 2).reshape(Q, world * k)
+        if fused:
+            rows, scores = ops.topk_merge(all_rows, all_scores, k)
+        else:
+            rows, scores = _stable_topk(all_scores, all_rows, torch.zeros_like(all_rows, dtype=torch.bool), k)
+    if entities is not None:
+        entities = entities.to(device=device, dtype=torch.long)
+        rows = torch.where(rows >= 0, entities[rows.clamp(min=0)], rows)
+    return rows, scores
+
+
 def _module(model):
     wrappers = (torch.nn.DataParallel, torch.nn.parallel.DistributedDataParallel)
     return model.module if isinstance(model, wrappers) else model

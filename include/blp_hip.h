@@ -450,6 +450,42 @@ int blp_dkrl_rows(const int64_t *tok, const float *mask, int64_t n, int L, const
                   int64_t ldo, int32_t *bad_tok, int device, void *stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Filtered top-k entity prediction: ANSWER a query (h, r, ?) / (?, r, t) with the k table rows the model scores highest,
+ * the known edges left out -- what a trained link predictor is used for (inductive BLP: the table holds the encoded new
+ * entities).  The (Q, N) score matrix of score_fn(ent_emb, ...) (models.py:222-248; train.py:146-147) is never built.
+ *
+ * Queries as in blp_rank_all_shard: Q = q_head + q_tail, head-replacing first; query q's fixed-entity vector is row
+ * fixed_row[q] of source (S, D) (row stride ld_src), its relation vector row rel_id[q] of rel_emb (R, D) contiguous.  A caller
+ * with loose query vectors (an entity that is not in the table) passes them as `source` with fixed_row = 0, 1, ...
+ * Candidates: the rows of table (N, D) f32, row stride ld -- GLOBAL rows [row_base, row_base + N) (a candidate shard).
+ * Output per query, k slots: rows (Q, k) int64 global rows, scores (Q, k) f32:
+ *   scores are score_fn's values bit for bit (the torch-CPU order of oracle/blp_oracle.c, sign of zero included);
+ *   order: descending score by IEEE comparison, equal scores (-0 == +0) by ascending row, NaN after every number (by row)
+ *          -- i.e. numpy's argsort(-score_row, kind="stable")[:k];
+ *   filter (optional): a blp_filter with blp_rank_all's semantics (segments of entity ids through ent2idx and row_base;
+ *          exclude[q] is never filtered) whose row_base MUST equal this call's (else BLP_ERR_BAD_ARG); filtered rows are
+ *          REMOVED, not demoted;
+ *   slots left over (k > N, or the filter leaves fewer than k rows): row -1, score NaN.
+ * Limits: 1 <= k <= 256 and D in {64, 128, 256} (blp_topk_supported); row_base + N <= 2^31; Q x k < 2^31; table / source /
+ * rel_emb 16-byte aligned, ld % 4 == 0, ld_src % 4 == 0.
+ * Workspace: blp_topk_workspace_bytes(...) bytes, 256-B aligned.  It does not grow with N beyond N = 2^17 rows and is bounded
+ * by 8 (D + k) Q + 4 MiB bytes (the queries' coefficient rows and at most Q + 16 384 partial lists of k 8-byte keys).
+ * Deterministic: the result does not depend on the grid, the device or the order of the candidates' evaluation.
+ * -------------------------------------------------------------------------------------------- */
+int blp_topk_supported(int model, int D, int k);
+size_t blp_topk_workspace_bytes(int model, int64_t N, int D, int64_t q_head, int64_t q_tail, int k);
+int blp_topk(int model, const float *table, int64_t N, int D, int64_t ld, int64_t row_base, const float *source, int64_t S,
+             int64_t ld_src, const int64_t *fixed_row, const float *rel_emb, int64_t R, const int64_t *rel_id, int64_t q_head,
+             int64_t q_tail, int k, const blp_filter *filter, int64_t *rows, float *scores, void *workspace,
+             size_t workspace_bytes, int device, void *stream);
+/* Merge `lists` per-query lists -- e.g. the blp_topk results of several candidate shards, gathered side by side: rows / scores
+ * (Q, lists x k_in), each list of k_in slots in blp_topk's order -- into the k best per query (rows_out, scores_out (Q, k)),
+ * by the same order; a row < 0 is an empty slot and sorts last.  Rows must be below 2^31.  Scores are copied (a NaN comes
+ * out as the quiet NaN 0x7fc00000).  The second stage of blp_topk, on caller-given lists; no workspace. */
+int blp_topk_merge(const int64_t *rows, const float *scores, int64_t Q, int lists, int k_in, int k, int64_t *rows_out,
+                   float *scores_out, int device, void *stream);
+
+/* --------------------------------------------------------------------------------------------
  * Test / A-B hooks -- NOT part of the production library.  They are compiled only with -DBLP_TEST_HOOKS, into a second
  * library (blp_amd/libblp_hip.hooks.so) that tests/ and tools/ load; libblp_hip.so exports neither symbol and has no
  * mutable process-wide state.  The library never reads the environment; the kernel-selection and slab-size overrides the
