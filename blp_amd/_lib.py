@@ -26,7 +26,8 @@ SYMBOLS = ("blp_version", "blp_last_error", "blp_device_caps", "blp_selftest", "
            "blp_rank_all_batches_native16", "blp_profile_next_rank_kernel", "blp_rank_all_prepass_stats", "blp_rank_from_scores",
            "blp_rank_metrics", "blp_rank_metric_sums", "blp_score_fwd", "blp_score_bwd", "blp_inbatch_loss_save_floats",
            "blp_inbatch_loss_fwd_launches", "blp_inbatch_loss_fwd", "blp_inbatch_loss_bwd", "blp_project_rows_supported", "blp_project_rows", "blp_bow_rows_supported", "blp_bow_rows", "blp_dkrl_rows_supported", "blp_dkrl_rows",
-           "blp_build_queries", "blp_topk_supported", "blp_topk_workspace_bytes", "blp_topk", "blp_topk_merge")
+           "blp_build_queries", "blp_topk_supported", "blp_topk_workspace_bytes", "blp_topk", "blp_topk_merge",
+           "blp_rerank_supported", "blp_rerank_cosine", "blp_rerank_ndcg")
 HOOK_SYMBOLS = ("blp_debug_set_knob", "blp_debug_gemm_dump", "blp_debug_reset_selftest")  # libblp_hip.hooks.so only
 KNOBS = ("rank_kernel", "gemm_kernel", "sad_queries_per_group", "sad_pass_groups", "sad_min_queries",
          "gemm_pass_words", "gemm_tiles_per_chunk", "exact_query_chunk",
@@ -44,6 +45,8 @@ def inbatch_save_floats(model_id, B, K, D):
 
 
 METRIC_SUMS_DOUBLES = 520  # BLP_METRIC_SUMS_DOUBLES: room the `sums` argument of blp_rank_metric_sums needs
+RERANK_MAX_SEGMENT = 8192  # BLP_RERANK_MAX_SEGMENT: candidates per query blp_rerank_ndcg takes
+RERANK_MAX_CUTOFFS = 8     # BLP_RERANK_MAX_CUTOFFS
 
 
 class HipLibraryError(RuntimeError):
@@ -195,6 +198,13 @@ def _load(path, hooks):
                            ctypes.POINTER(BlpFilter), _vp, _vp, _vp, _sz, _i, _vp]
     L.blp_topk_merge.restype = _i
     L.blp_topk_merge.argtypes = [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _vp]
+    L.blp_rerank_supported.restype = _i
+    L.blp_rerank_supported.argtypes = [_i64, _i]
+    L.blp_rerank_cosine.restype = _i
+    L.blp_rerank_cosine.argtypes = [_vp, _i64, _i, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i, _vp]
+    L.blp_rerank_ndcg.restype = _i
+    L.blp_rerank_ndcg.argtypes = [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, _vp, _i64,
+                                  _vp, _vp, _i, _vp]
     if hooks:
         L.blp_debug_gemm_dump.restype = _i
         L.blp_debug_gemm_dump.argtypes = [_vp, _vp]

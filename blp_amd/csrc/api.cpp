@@ -724,4 +724,61 @@ int blp_topk_merge(const int64_t* rows, const float* scores, int64_t Q, int list
     return BLP_OK;
 }
 
+// ---- re-ranking a retrieval run (rerank.hip)
+static_assert(BLP_RERANK_MAX_SEGMENT == blp::kRerankMaxSegment && BLP_RERANK_MAX_CUTOFFS == blp::kRerankMaxCutoffs,
+              "include/blp_hip.h and launch.h disagree on the re-ranking limits");
+
+int blp_rerank_supported(int64_t max_segment, int D) {
+    return max_segment >= 0 && max_segment <= BLP_RERANK_MAX_SEGMENT && D >= 1 ? 1 : 0;
+}
+
+int blp_rerank_cosine(const float* table, int64_t E, int D, int64_t ld, const float* query, int64_t Q, int64_t ldq,
+                      const int64_t* cand_ptr, const int32_t* cand_row, int64_t C, float* s1, int device, void* stream) {
+    if (D < 1 || E < 0 || Q < 0 || C < 0 || ld < D || ldq < D)
+        return fail(BLP_ERR_BAD_ARG, "blp_rerank_cosine: D < 1, negative size or row stride below D (E=%lld Q=%lld C=%lld ld=%lld "
+                    "ldq=%lld D=%d)", (long long)E, (long long)Q, (long long)C, (long long)ld, (long long)ldq, D);
+    if (C >= (1ll << 31)) return fail(BLP_ERR_BAD_ARG, "blp_rerank_cosine: C = %lld candidates, at most 2^31 - 1", (long long)C);
+    if (C > 0 && Q == 0) return fail(BLP_ERR_BAD_ARG, "blp_rerank_cosine: %lld candidates but no query", (long long)C);
+    if (C == 0) return BLP_OK;
+    if (!cand_ptr || !cand_row || !s1 || !query || (E > 0 && !table))
+        return fail(BLP_ERR_BAD_ARG, "blp_rerank_cosine: NULL table / query / cand_ptr / cand_row / s1");
+    DeviceGuard guard(device);
+    if (guard.error() != hipSuccess) return hip_fail(guard.error(), "hipSetDevice");
+    hipError_t err = blp::launch_rerank_cosine(table, E, D, ld, query, Q, ldq, cand_ptr, cand_row, C, s1,
+                                               static_cast<hipStream_t>(stream));
+    if (err != hipSuccess) return hip_fail(err, "blp_rerank_cosine launch");
+    return BLP_OK;
+}
+
+int blp_rerank_ndcg(const float* s1, const double* s2, const int32_t* gain, const int64_t* cand_ptr, int64_t Q, int64_t C,
+                    int64_t max_segment, const double* alphas, int A, const int32_t* cutoffs, int n_cut,
+                    const double* log2_table, int64_t n_log2, const double* idcg, double* ndcg, int device, void* stream) {
+    if (max_segment > BLP_RERANK_MAX_SEGMENT)
+        return fail(BLP_ERR_BAD_ARG, "blp_rerank_ndcg: a segment of %lld candidates exceeds the limit of %d candidates per query",
+                    (long long)max_segment, BLP_RERANK_MAX_SEGMENT);
+    if (Q < 0 || C < 0 || A < 0 || max_segment < 0 || Q >= (1ll << 31))
+        return fail(BLP_ERR_BAD_ARG, "blp_rerank_ndcg: negative Q / C / A / max_segment, or Q >= 2^31");
+    if (!cutoffs || n_cut < 1 || n_cut > BLP_RERANK_MAX_CUTOFFS)
+        return fail(BLP_ERR_BAD_ARG, "blp_rerank_ndcg: 1 to %d cutoffs (a host array), got %d", BLP_RERANK_MAX_CUTOFFS, n_cut);
+    blp::RerankCutoffs cuts{};
+    cuts.n = n_cut;
+    for (int j = 0; j < n_cut; ++j) {
+        if (cutoffs[j] < 1 || (j > 0 && cutoffs[j] <= cutoffs[j - 1]))
+            return fail(BLP_ERR_BAD_ARG, "blp_rerank_ndcg: cutoffs must be >= 1 and strictly ascending");
+        cuts.k[j] = cutoffs[j];
+    }
+    if (n_log2 < cuts.k[n_cut - 1])
+        return fail(BLP_ERR_BAD_ARG, "blp_rerank_ndcg: log2_table holds %lld entries, the largest cutoff needs %d", (long long)n_log2,
+                    cuts.k[n_cut - 1]);
+    if (Q == 0 || A == 0) return BLP_OK;
+    if (!cand_ptr || !alphas || !log2_table || !idcg || !ndcg || (C > 0 && (!s1 || !s2 || !gain)))
+        return fail(BLP_ERR_BAD_ARG, "blp_rerank_ndcg: NULL pointer");
+    DeviceGuard guard(device);
+    if (guard.error() != hipSuccess) return hip_fail(guard.error(), "hipSetDevice");
+    hipError_t err = blp::launch_rerank_ndcg(s1, s2, gain, cand_ptr, Q, C, alphas, A, cuts, log2_table, idcg, max_segment, ndcg,
+                                             static_cast<hipStream_t>(stream));
+    if (err != hipSuccess) return hip_fail(err, "blp_rerank_ndcg launch");
+    return BLP_OK;
+}
+
 }  // extern "C"

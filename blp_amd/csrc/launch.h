@@ -97,6 +97,19 @@ hipError_t launch_topk(int model, int D, const float* table, int64_t N, int64_t 
 hipError_t launch_topk_merge(const int64_t* rows, const float* scores, int64_t Q, int64_t n_in, int k, int64_t* rows_out,
                              float* scores_out, hipStream_t stream);
 
+// rerank.hip: re-ranking a retrieval run (include/blp_hip.h: blp_rerank_cosine, blp_rerank_ndcg)
+constexpr int kRerankMaxSegment = 8192;  // candidates per query: 8 192 keys of 8 bytes = 64 KiB of LDS
+constexpr int kRerankMaxCutoffs = 8;
+struct RerankCutoffs {  // ascending cutoffs, passed by value as a kernel argument
+    int n;
+    int k[kRerankMaxCutoffs];
+};
+hipError_t launch_rerank_cosine(const float* table, int64_t E, int D, int64_t ld, const float* query, int64_t Q, int64_t ldq,
+                                const int64_t* cand_ptr, const int32_t* cand_row, int64_t C, float* s1, hipStream_t stream);
+hipError_t launch_rerank_ndcg(const float* s1, const double* s2, const int32_t* gain, const int64_t* cand_ptr, int64_t Q,
+                              int64_t C, const double* alphas, int A, const RerankCutoffs& cuts, const double* log2_table,
+                              const double* idcg, int64_t max_segment, double* ndcg, hipStream_t stream);
+
 hipError_t launch_rank_metrics(const int32_t* counts, int64_t Q, const int32_t* k, float* rr,
                                uint8_t* hits, hipStream_t stream);
 

@@ -4,6 +4,8 @@ device memory and the stream; every arithmetic step of the hot path runs in the 
     rank_all(...)       all-entities ranking counts        (train.py:146-171, utils.py:103-105)
     rank_metrics(...)   counts -> reciprocal ranks, hits   (utils.py:104-109)
     topk(...)           filtered top-k prediction per query (no score matrix)
+    rerank_cosine(...)  cosine of every retrieval candidate with its query (retrieval.py:170-175)
+    rerank_ndcg(...)    trec_eval ndcg_cut of every (alpha, query) of a re-ranked run (retrieval.py:139-258)
     score(...)          score_fn(heads, tails, rels)       (models.py:222-248), differentiable
     inbatch_loss(...)   compute_loss on in-batch negatives (models.py:51-70), differentiable
 
@@ -424,6 +426,77 @@ def topk_merge(rows, scores, k):
     if status:
         _lib.check(status, "blp_topk_merge")
     return rows_out, scores_out
+
+
+def rerank_supported(max_segment, dim):
+    """True if rerank_cosine / rerank_ndcg take segments of ``max_segment`` candidates and width ``dim``
+    (include/blp_hip.h: blp_rerank_supported)."""
+    return bool(_lib.lib().blp_rerank_supported(int(max_segment), int(dim)))
+
+
+def _i64_flat(t):
+    return t.reshape(-1).to(torch.int64).contiguous()
+
+
+def rerank_cosine(table, queries, cand_ptr, cand_row, out=None):
+    """blp_rerank_cosine: s1 (C,) float32 = F.normalize(table[cand_row[c]]) . F.normalize(queries[q]) for the candidates c of
+    query q ([cand_ptr[q], cand_ptr[q + 1])), 0.0 where cand_row is -1 (retrieval.py:170-175; the summation order is
+    blp_amd.retrieval.cosine_restated's)."""
+    _require_device(table, queries, cand_ptr, cand_row, out)
+    table = _f32_rows(table, "table")
+    queries = _f32_rows(queries, "queries")
+    if table.dim() != 2 or queries.dim() != 2 or queries.shape[1] != table.shape[1]:
+        raise ValueError(f"table (E, D) and queries (Q, D) of the same width, got {tuple(table.shape)} / {tuple(queries.shape)}")
+    E, D = table.shape
+    Q = queries.shape[0]
+    cand_ptr = _i64_flat(cand_ptr)
+    cand_row = cand_row.reshape(-1).to(torch.int32).contiguous()
+    C = cand_row.shape[0]
+    if cand_ptr.shape[0] != Q + 1:
+        raise ValueError(f"cand_ptr must hold Q + 1 = {Q + 1} offsets, got {cand_ptr.shape[0]}")
+    dev = table.device
+    if out is None:
+        out = torch.empty(C, dtype=torch.float32, device=dev)
+    if out.shape != (C,) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous (C,) float32 tensor")
+    status = _lib.lib().blp_rerank_cosine(_addr(table), E, D, table.stride(0) if E > 1 else D, _addr(queries), Q,
+                                          queries.stride(0) if Q > 1 else D, _addr(cand_ptr), _addr(cand_row), C, _addr(out),
+                                          dev.index, _stream(dev))
+    _lib.check(status, "blp_rerank_cosine")
+    return out
+
+
+def rerank_ndcg(s1, s2, gain, cand_ptr, alphas, cutoffs, log2_table, idcg, max_segment=None, out=None):
+    """blp_rerank_ndcg: (A, Q, len(cutoffs)) float64, trec_eval's ndcg_cut of the run alpha * s1 + (1 - alpha) * s2 for every
+    alpha and query (each segment ordered by docno descending).  ``cutoffs`` is a host sequence; ``max_segment``
+    bounds the segment lengths (None: read from cand_ptr, one host synchronisation)."""
+    _require_device(s1, s2, gain, cand_ptr, alphas, log2_table, idcg, out)
+    dev = s1.device
+    s1 = s1.reshape(-1).to(torch.float32).contiguous()
+    s2 = s2.reshape(-1).to(torch.float64).contiguous()
+    gain = gain.reshape(-1).to(torch.int32).contiguous()
+    cand_ptr = _i64_flat(cand_ptr)
+    alphas = alphas.reshape(-1).to(torch.float64).contiguous()
+    log2_table = log2_table.reshape(-1).to(torch.float64).contiguous()
+    cutoffs = [int(k) for k in cutoffs]
+    Q, C, A, n_cut = cand_ptr.shape[0] - 1, s1.shape[0], alphas.shape[0], len(cutoffs)
+    if Q < 0 or s2.shape[0] != C or gain.shape[0] != C:
+        raise ValueError("s1, s2 and gain need one entry per candidate; cand_ptr Q + 1 offsets")
+    idcg = idcg.to(torch.float64).contiguous()
+    if idcg.shape != (Q, n_cut):
+        raise ValueError(f"idcg must be (Q, n_cut) = ({Q}, {n_cut}), got {tuple(idcg.shape)}")
+    if max_segment is None:
+        max_segment = int((cand_ptr[1:] - cand_ptr[:-1]).max()) if Q > 0 else 0
+    if out is None:
+        out = torch.empty((A, Q, n_cut), dtype=torch.float64, device=dev)
+    if out.shape != (A, Q, n_cut) or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous (A, Q, n_cut) float64 tensor")
+    k = (ctypes.c_int32 * max(1, n_cut))(*cutoffs)
+    status = _lib.lib().blp_rerank_ndcg(_addr(s1), _addr(s2), _addr(gain), _addr(cand_ptr), Q, C, int(max_segment), _addr(alphas),
+                                        A, k, n_cut, _addr(log2_table), log2_table.shape[0], _addr(idcg), _addr(out), dev.index,
+                                        _stream(dev))
+    _lib.check(status, "blp_rerank_ndcg")
+    return out
 
 
 def rank_all_batches(rel_model, table, fixed_row, rel_emb, rel_ids, true_row, num_triples, batch, filter=None, out=None, source=None,

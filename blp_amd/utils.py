@@ -34,6 +34,29 @@ def get_model(model, dim, rel_model, loss_fn, num_entities, num_relations, encod
         raise ValueError(f"Unkown model {model}")
 
 
+def text_tokenizer(model, encoder_name, data_root):
+    """The description tokenizer of ``model``: BERT's for the BERT encoders, else the GloVe word map under ``data_root``
+    (train.py and retrieval.py)."""
+    import os.path as osp
+    if model.startswith('bert') or model == 'blp':
+        from transformers import BertTokenizer
+        return BertTokenizer.from_pretrained(encoder_name)
+    from .data import GloVeTokenizer
+    return GloVeTokenizer(osp.join(data_root, 'glove', 'glove.6B.300d-maps.pt'))
+
+
+def text_model(model, dim, rel_model, loss_fn, num_entities, num_relations, encoder_name, regularizer, data_root):
+    """get_model, with the GloVe table read from ``data_root`` when that is not the reference's 'data' (train.py and
+    retrieval.py)."""
+    if model in ('glove-bow', 'glove-dkrl') and data_root != 'data':
+        import os.path as osp
+        emb = osp.join(data_root, 'glove', 'glove.6B.300d.pt')
+        if model == 'glove-bow':
+            return models.BOW(rel_model, loss_fn, num_relations, regularizer, embeddings=emb)
+        return models.DKRL(dim, rel_model, loss_fn, num_relations, regularizer, embeddings=emb)
+    return get_model(model, dim, rel_model, loss_fn, num_entities, num_relations, encoder_name, regularizer)
+
+
 def make_ent2idx(entities, max_ent_id):
     """Tensor indexed by entity id holding the entity's position in ``entities`` (-1 if absent).
 

@@ -486,6 +486,40 @@ int blp_topk_merge(const int64_t *rows, const float *scores, int64_t Q, int list
                    float *scores_out, int device, void *stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Re-ranking a first-stage retrieval run (reference retrieval.py rerank: BM25F candidates of DBpedia-Entity v2 re-scored
+ * with entity embeddings, the mixing weight alpha chosen per fold by nDCG@100).  Candidates are a CSR over Q queries:
+ * query q owns candidates [cand_ptr[q], cand_ptr[q + 1]) (cand_ptr (Q + 1) int64, cand_ptr[0] = 0, cand_ptr[Q] = C).
+ *
+ * blp_rerank_supported(max_segment, D): 1 if both kernels take segments of up to max_segment candidates and embeddings of
+ *   width D (any D >= 1; max_segment <= BLP_RERANK_MAX_SEGMENT).
+ *
+ * blp_rerank_cosine: s1 (C) f32 = F.normalize(table[cand_row[c]]) . F.normalize(query[q]) (retrieval.py:170-175) -- table
+ *   (E, D) f32, row stride ld; query (Q, D) f32, row stride ldq; cand_row (C) int32, -1 = the entity has no description:
+ *   s1 = 0.0f exactly (the reference's literal 0).  Norms n = sqrtf(sum x^2), x_i / max(n, 1e-12f), division and square
+ *   root correctly rounded; every sum in one fixed order (stated in blp_amd/csrc/rerank.hip; blp_amd.retrieval.
+ *   cosine_restated restates it bit for bit).  A row outside [-1, E) gives NaN.
+ *
+ * blp_rerank_ndcg: ndcg (A, Q, n_cut) f64 = trec_eval's ndcg_cut of every (alphas[a], query):
+ *   c = alpha * s1 + (1 - alpha) * s2 in f64 (s2 (C) f64: the first-stage scores); candidates ranked by (float)c descending,
+ *   ties (-0 == +0) by the LOWER index within the segment -- the caller orders each segment by docno descending, trec_eval's
+ *   tie-break --, NaN last; DCG@k = sum over the first min(k, n) ranks i with gain > 0 of gain / log2_table[i], added in rank
+ *   order in f64 (gain (C) int32: the qrels relevance, 0 if unjudged); nDCG = DCG / idcg[q, j] if idcg > 0, else 0.
+ *   cutoffs: a HOST array of n_cut (1..BLP_RERANK_MAX_CUTOFFS) ascending cutoffs >= 1; log2_table (n_log2 >= the last cutoff)
+ *   f64 = log2(i + 2); idcg (Q, n_cut) f64; alphas (A) f64.  max_segment: the caller's bound on cand_ptr[q + 1] - cand_ptr[q]
+ *   (it sizes the launch); above BLP_RERANK_MAX_SEGMENT the call is refused (BLP_ERR_BAD_ARG); a segment longer than the
+ *   given bound gets NaN results.
+ * Both: no workspace, asynchronous, deterministic.
+ * -------------------------------------------------------------------------------------------- */
+#define BLP_RERANK_MAX_SEGMENT 8192
+#define BLP_RERANK_MAX_CUTOFFS 8
+int blp_rerank_supported(int64_t max_segment, int D);
+int blp_rerank_cosine(const float *table, int64_t E, int D, int64_t ld, const float *query, int64_t Q, int64_t ldq,
+                      const int64_t *cand_ptr, const int32_t *cand_row, int64_t C, float *s1, int device, void *stream);
+int blp_rerank_ndcg(const float *s1, const double *s2, const int32_t *gain, const int64_t *cand_ptr, int64_t Q, int64_t C,
+                    int64_t max_segment, const double *alphas, int A, const int32_t *cutoffs, int n_cut,
+                    const double *log2_table, int64_t n_log2, const double *idcg, double *ndcg, int device, void *stream);
+
+/* --------------------------------------------------------------------------------------------
  * Test / A-B hooks -- NOT part of the production library.  They are compiled only with -DBLP_TEST_HOOKS, into a second
  * library (blp_amd/libblp_hip.hooks.so) that tests/ and tools/ load; libblp_hip.so exports neither symbol and has no
  * mutable process-wide state.  The library never reads the environment; the kernel-selection and slab-size overrides the

@@ -101,21 +101,8 @@ def _linear_schedule_with_warmup(optimizer, num_warmup_steps, num_training_steps
     return torch.optim.lr_scheduler.LambdaLR(optimizer, factor)
 
 
-def _tokenizer(model, encoder_name, data_root):
-    if model.startswith('bert') or model == 'blp':
-        from transformers import BertTokenizer
-        return BertTokenizer.from_pretrained(encoder_name)
-    return GloVeTokenizer(osp.join(data_root, 'glove', 'glove.6B.300d-maps.pt'))
-
-
-def _get_model(model, dim, rel_model, loss_fn, num_entities, num_relations, encoder_name, regularizer, data_root):
-    if model in ('glove-bow', 'glove-dkrl') and data_root != 'data':
-        from blp_amd import models as m
-        emb = osp.join(data_root, 'glove', 'glove.6B.300d.pt')
-        if model == 'glove-bow':
-            return m.BOW(rel_model, loss_fn, num_relations, regularizer, embeddings=emb)
-        return m.DKRL(dim, rel_model, loss_fn, num_relations, regularizer, embeddings=emb)
-    return utils.get_model(model, dim, rel_model, loss_fn, num_entities, num_relations, encoder_name, regularizer)
+_tokenizer = utils.text_tokenizer  # (shared with retrieval.py)
+_get_model = utils.text_model
 
 
 @ex.command
