@@ -663,33 +663,39 @@ size_t blp_topk_workspace_bytes(int model, int64_t N, int D, int64_t q_head, int
     return blp::topk_workspace_bytes(model, D, N, q_head, q_tail, k);
 }
 
-int blp_topk(int model, const float* table, int64_t N, int D, int64_t ld, int64_t row_base, const float* source, int64_t S,
-             int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R, const int64_t* rel_id, int64_t q_head,
-             int64_t q_tail, int k, const blp_filter* filter, int64_t* rows, float* scores, void* workspace,
-             size_t workspace_bytes, int device, void* stream) {
-    if (!valid_model(model)) return fail(BLP_ERR_BAD_ARG, "blp_topk: unknown model %d", model);
-    if (k < 1 || k > 256) return fail(BLP_ERR_BAD_ARG, "blp_topk: k = %d outside [1, 256]", k);
+// blp_topk and blp_topk_typed: the argument checks (messages under the entry's name `who`), then the launch
+static int topk_call(const char* who, int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld,
+                     int64_t row_base, const float* source, int64_t S, int64_t ld_src, const int64_t* fixed_row,
+                     const float* rel_emb, int64_t R, const int64_t* rel_id, int64_t q_head, int64_t q_tail, int k,
+                     const blp_filter* filter, int64_t* rows, float* scores, void* workspace, size_t workspace_bytes, int device,
+                     void* stream) {
+    if (!valid_model(model)) return fail(BLP_ERR_BAD_ARG, "%s: unknown model %d", who, model);
+    if (!valid_table_dtype(table_dtype)) return fail(BLP_ERR_BAD_ARG, "%s: unknown table dtype %d", who, table_dtype);
+    if (k < 1 || k > 256) return fail(BLP_ERR_BAD_ARG, "%s: k = %d outside [1, 256]", who, k);
     if (!blp_topk_supported(model, D, k))
-        return fail(BLP_ERR_UNSUPPORTED_DIM, "blp_topk: D = %d not supported (64 / 128 / 256: see blp_topk_supported)", D);
+        return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (64 / 128 / 256: see blp_topk_supported)", who, D);
     if (N < 0 || q_head < 0 || q_tail < 0 || ld < D || row_base < 0)
-        return fail(BLP_ERR_BAD_ARG, "blp_topk: negative size / row_base or ld < D (N=%lld q_head=%lld q_tail=%lld ld=%lld)",
+        return fail(BLP_ERR_BAD_ARG, "%s: negative size / row_base or ld < D (N=%lld q_head=%lld q_tail=%lld ld=%lld)", who,
                     (long long)N, (long long)q_head, (long long)q_tail, (long long)ld);
     if (row_base + N > (1ll << 31) || q_head + q_tail > (1ll << 31) / k)
-        return fail(BLP_ERR_BAD_ARG, "blp_topk: global rows must stay below 2^31 and Q x k below 2^31");
-    if (!rows || !scores) return fail(BLP_ERR_BAD_ARG, "blp_topk: NULL rows / scores");
+        return fail(BLP_ERR_BAD_ARG, "%s: global rows must stay below 2^31 and Q x k below 2^31", who);
+    if (!rows || !scores) return fail(BLP_ERR_BAD_ARG, "%s: NULL rows / scores", who);
     const int64_t Q = q_head + q_tail;
     if (Q > 0 && (!source || !fixed_row || !rel_id || !rel_emb || R <= 0 || S <= 0))
-        return fail(BLP_ERR_BAD_ARG, "blp_topk: NULL source / fixed_row / rel_id / rel_emb, or R <= 0 / S <= 0");
-    if (N > 0 && !table) return fail(BLP_ERR_BAD_ARG, "blp_topk: NULL table");
-    if (!aligned16(table) || (ld & 3) || !aligned16(source) || (ld_src & 3) || ld_src < D || !aligned16(rel_emb))
-        return fail(BLP_ERR_BAD_ARG, "blp_topk: table / source / rel_emb must be 16-byte aligned, ld %% 4 == 0, ld_src %% 4 == 0, "
-                                     "ld_src >= D");
+        return fail(BLP_ERR_BAD_ARG, "%s: NULL source / fixed_row / rel_id / rel_emb, or R <= 0 / S <= 0", who);
+    if (N > 0 && !table) return fail(BLP_ERR_BAD_ARG, "%s: NULL table", who);
+    if (!table_rows_aligned(table, table_dtype, ld) || !aligned16(source) || (ld_src & 3) || ld_src < D || !aligned16(rel_emb))
+        return fail(BLP_ERR_BAD_ARG, table_dtype == BLP_DTYPE_F32
+                                         ? "%s: table / source / rel_emb must be 16-byte aligned, ld %% 4 == 0, ld_src %% 4 == 0, ld_src >= D"
+                                         : "%s: table / source / rel_emb must be 16-byte aligned, ld %% 8 == 0 (a 16-bit table's row stride, "
+                                           "in elements), ld_src %% 4 == 0, ld_src >= D",
+                    who);
     blp::FilterSpec spec;
     if (filter) {
         if (!filter->seg_lo || !filter->seg_hi || !filter->values || (filter->ent2idx && filter->ent2idx_len < 0))
-            return fail(BLP_ERR_BAD_ARG, "blp_topk: filter needs seg_lo, seg_hi and values (ent2idx_len >= 0)");
+            return fail(BLP_ERR_BAD_ARG, "%s: filter needs seg_lo, seg_hi and values (ent2idx_len >= 0)", who);
         if (filter->row_base != row_base)
-            return fail(BLP_ERR_BAD_ARG, "blp_topk: filter row_base %lld differs from the call's row_base %lld",
+            return fail(BLP_ERR_BAD_ARG, "%s: filter row_base %lld differs from the call's row_base %lld", who,
                         (long long)filter->row_base, (long long)row_base);
         spec.lo = filter->seg_lo; spec.hi = filter->seg_hi; spec.val = filter->values; spec.exclude = filter->exclude;
         spec.ent2idx = filter->ent2idx; spec.ent2idx_len = filter->ent2idx ? filter->ent2idx_len : 0;
@@ -698,15 +704,41 @@ int blp_topk(int model, const float* table, int64_t N, int D, int64_t ld, int64_
     if (Q == 0) return BLP_OK;
     const size_t need = blp::topk_workspace_bytes(model, D, N, q_head, q_tail, k);
     if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255u))
-        return fail(BLP_ERR_WORKSPACE, "blp_topk: workspace must be 256-byte aligned and >= %zu bytes (got %zu)", need,
+        return fail(BLP_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned and >= %zu bytes (got %zu)", who, need,
                     workspace_bytes);
     DeviceGuard guard(device);
     if (guard.error() != hipSuccess) return hip_fail(guard.error(), "hipSetDevice");
-    hipError_t err = blp::launch_topk(model, D, table, N, ld, row_base, blp::QRows::rows_of(source, fixed_row, ld_src),
+    hipError_t err = blp::launch_topk(model, D, table_dtype, table, N, ld, row_base, blp::QRows::rows_of(source, fixed_row, ld_src),
                                       blp::QRows::rows_of(rel_emb, rel_id, D), q_head, q_tail, k, spec, rows, scores, workspace,
                                       static_cast<hipStream_t>(stream));
-    if (err != hipSuccess) return hip_fail(err, "blp_topk launch");
+    if (err != hipSuccess) return hip_fail(err, table_dtype == BLP_DTYPE_F32 ? "blp_topk launch" : "blp_topk_typed launch");
     return BLP_OK;
+}
+
+int blp_topk(int model, const float* table, int64_t N, int D, int64_t ld, int64_t row_base, const float* source, int64_t S,
+             int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R, const int64_t* rel_id, int64_t q_head,
+             int64_t q_tail, int k, const blp_filter* filter, int64_t* rows, float* scores, void* workspace,
+             size_t workspace_bytes, int device, void* stream) {
+    return topk_call("blp_topk", model, table, BLP_DTYPE_F32, N, D, ld, row_base, source, S, ld_src, fixed_row, rel_emb, R, rel_id,
+                     q_head, q_tail, k, filter, rows, scores, workspace, workspace_bytes, device, stream);
+}
+
+int blp_topk_typed_supported(int model, int table_dtype, int D, int k) {
+    return valid_model(model) && blp::topk_typed_supported(model, table_dtype, D, k) ? 1 : 0;
+}
+
+size_t blp_topk_typed_workspace_bytes(int model, int table_dtype, int64_t N, int D, int64_t q_head, int64_t q_tail, int k) {
+    if (!blp_topk_typed_supported(model, table_dtype, D, k)) return 0;
+    return blp::topk_workspace_bytes(model, D, N, q_head, q_tail, k);
+}
+
+int blp_topk_typed(int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld, int64_t row_base,
+                   const float* source, int64_t S, int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R,
+                   const int64_t* rel_id, int64_t q_head, int64_t q_tail, int k, const blp_filter* filter, int64_t* rows,
+                   float* scores, void* workspace, size_t workspace_bytes, int device, void* stream) {
+    return topk_call(table_dtype == BLP_DTYPE_F32 ? "blp_topk" : "blp_topk_typed", model, table, table_dtype, N, D, ld, row_base,
+                     source, S, ld_src, fixed_row, rel_emb, R, rel_id, q_head, q_tail, k, filter, rows, scores, workspace,
+                     workspace_bytes, device, stream);
 }
 
 int blp_topk_merge(const int64_t* rows, const float* scores, int64_t Q, int lists, int k_in, int k, int64_t* rows_out,

@@ -88,10 +88,12 @@ hipError_t launch_rank_all_batches16(int model, int D, const void* table, int dt
 hipError_t launch_prep_coef(int model, int D, const QRows q_fixed, const QRows q_rel, int64_t q_head, int64_t q_tail,
                             float* coef_head, float* coef_tail, hipStream_t stream);
 
-// topk.hip: filtered top-k over the candidate table (include/blp_hip.h: blp_topk, blp_topk_merge)
+// topk.hip: filtered top-k over the candidate table (include/blp_hip.h: blp_topk, blp_topk_typed, blp_topk_merge); the
+// table f32 or 16-bit (dtype: table_elem.h; the workspace does not depend on it)
 bool topk_supported(int model, int D, int k);
+bool topk_typed_supported(int model, int dtype, int D, int k);
 size_t topk_workspace_bytes(int model, int D, int64_t N, int64_t q_head, int64_t q_tail, int k);
-hipError_t launch_topk(int model, int D, const float* table, int64_t N, int64_t ld, int64_t row_base, const QRows q_fixed,
+hipError_t launch_topk(int model, int D, int dtype, const void* table, int64_t N, int64_t ld, int64_t row_base, const QRows q_fixed,
                        const QRows q_rel, int64_t q_head, int64_t q_tail, int k, const FilterSpec& filter, int64_t* rows,
                        float* scores, void* workspace, hipStream_t stream);
 hipError_t launch_topk_merge(const int64_t* rows, const float* scores, int64_t Q, int64_t n_in, int k, int64_t* rows_out,

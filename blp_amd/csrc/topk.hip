@@ -27,12 +27,22 @@
 // Grid of topk_tiles: (query chunk x candidate slab), bounded: few queries against a long table -> one chunk, up to
 // kTopkTargetGroups slabs grid-striding over the tiles (HBM-bound); many queries -> one slab per chunk, the table re-read from
 // L2 by every chunk (VALU-bound).  Nothing is dynamically indexed in registers: lists live in LDS.
+//
+// A 16-BIT TABLE (blp_topk_typed; table_elem.h): topk_tiles16 is topk_tiles with another row loader, Rows16.  A row-piece is
+// 64 columns per 128-byte line (rank_stream16.hip's layout): the loads and the transposing LDS slab carry the 16-bit words,
+// and a lane widens its row (exactly) only after the transpose, into the same e[D] the f32 kernel scores.  The loads of a
+// tile are issued when the tile is taken, as load_tile issues the f32 kernel's (loads issued one tile ahead kept
+// their buffer in scratch).  topk_rescore reads the winners from the 16-bit table, widened.  The result is blp_topk's on the
+// table widened to f32.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "launch.h"
 #include "rank_common.h"
 #include "score_core.h"
+#include "table_elem.h"
 #include "tile.h"
 
 #pragma clang fp contract(off)
@@ -156,17 +166,71 @@ __device__ __forceinline__ void topk_side(const float (&e)[D], bool valid, int64
     }
 }
 
-template <int MODEL, int D>
-__global__ __launch_bounds__(kTopkWaves * 64, (D == 256 ? 1 : 2)) void topk_tiles_kernel(
-    const float* __restrict__ table, int64_t N, int64_t ld, int64_t row_base, const float* __restrict__ coef_head,
-    const float* __restrict__ coef_tail, int64_t q_head, int64_t q_tail, int q_chunk, int n_slabs, int k,
-    const FilterSpec filter, u64* __restrict__ partial) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lane = tid & 63;
-    float* slab = smem + wave * kSlabFloats;
-    u64* lists_all = reinterpret_cast<u64*>(smem + kTopkWaves * kSlabFloats);
+// Row loaders of the tile loop: take(e, t) puts tile t's rows in e[] (lane l <- row 64 t + l; rows past the end clamped to
+// the last row, the caller masks them).
+template <int D>
+struct RowsF32 {  // load_tile: every load of the tile, then the transpose
+    const float* __restrict__ table;
+    int64_t N, ld;
+    float* slab;
+    int lane;
+    __device__ __forceinline__ void take(float (&e)[D], int64_t t) {
+        load_tile<D, false>(e, table, N, ld, t * kTileRows, slab, lane);
+    }
+};
+
+// A 16-bit table (T = _Float16 / __bf16, row stride ld elements, rows 16-byte aligned): w[s][i] = this lane's 16 bytes of
+// piece s (columns 64 s ..) of row 8 i + lane / 8 -- 8 rows x 128 B per instruction, as rank_stream16.hip loads them.
+template <int D, class T>
+struct Rows16 {
+    static constexpr int NP = D / 64;
+    const char* __restrict__ table;
+    int64_t N, ld;
+    float* slab;
+    int lane;
+    uint4 w[NP][8];
+    __device__ __forceinline__ void fetch(int64_t t) {
+        static_for<8>([&](auto ii) {
+            constexpr int i = decltype(ii)::value;
+            int64_t row = t * kTileRows + 8 * i + (lane >> 3);
+            row = row < N ? row : N - 1;
+            const char* src = table + row * ld * 2 + (lane & 7) * 16;
+            static_for<NP>([&](auto ss) {
+                constexpr int s = decltype(ss)::value;
+                w[s][i] = *reinterpret_cast<const uint4*>(src + s * 128);
+            });
+        });
+    }
+    __device__ __forceinline__ void take(float (&e)[D], int64_t t) {
+        fetch(t);
+        float* wr = slab + (lane >> 3) * kLdsStride + (lane & 7) * 4;
+        const float* rd = slab + lane * kLdsStride;
+        static_for<NP>([&](auto ss) {
+            constexpr int s = decltype(ss)::value;
+            if (s > 0) wave_lds_sync();  // the previous piece's reads are done before the slab is rewritten
+            static_for<8>([&](auto ii) {
+                constexpr int i = decltype(ii)::value;
+                *reinterpret_cast<uint4*>(wr + 8 * i * kLdsStride) = w[s][i];
+            });
+            wave_lds_sync();
+            static_for<8>([&](auto jj) {  // the lane's row, columns 64 s + 8 j .. + 7 (element 2 m in word m's low half)
+                constexpr int j = decltype(jj)::value, c = 64 * s + 8 * j;
+                const uint4 v = *reinterpret_cast<const uint4*>(rd + 4 * j);
+                widen_pair<T>(v.x, e[c], e[c + 1]);
+                widen_pair<T>(v.y, e[c + 2], e[c + 3]);
+                widen_pair<T>(v.z, e[c + 4], e[c + 5]);
+                widen_pair<T>(v.w, e[c + 6], e[c + 7]);
+            });
+        });
+    }
+};
+
+// The body of topk_tiles over either loader.
+template <int MODEL, int D, class Rows>
+__device__ __forceinline__ void topk_tiles_run(Rows& rows, int64_t N, int64_t row_base, const float* __restrict__ coef_head,
+                                               const float* __restrict__ coef_tail, int64_t q_head, int64_t q_tail, int q_chunk,
+                                               int n_slabs, int k, const FilterSpec& filter, u64* __restrict__ partial,
+                                               u64* lists_all, int wave, int lane) {
     u64* lists = lists_all + (size_t)wave * q_chunk * k;
 
     const int64_t chunk = blockIdx.x / n_slabs;
@@ -186,7 +250,7 @@ __global__ __launch_bounds__(kTopkWaves * 64, (D == 256 ? 1 : 2)) void topk_tile
     for (int64_t t = (int64_t)s * kTopkWaves + wave; t < n_tiles; t += (int64_t)n_slabs * kTopkWaves) {
         float e[D];
         const int64_t row0 = t * kTileRows;
-        load_tile<D, false>(e, table, N, ld, row0, slab, lane);  // rows past the end are clamped, then masked
+        rows.take(e, t);
         const bool valid = row0 + lane < N;
         topk_side<MODEL, HEAD, D>(e, valid, row0, row_base, N, ch, h_lo, h_hi, qa, lists, k, filter, lane);
         topk_side<MODEL, TAIL, D>(e, valid, row0, row_base, N, ct, t_lo, t_hi, qa, lists, k, filter, lane);
@@ -204,6 +268,35 @@ __global__ __launch_bounds__(kTopkWaves * 64, (D == 256 ? 1 : 2)) void topk_tile
         u64* out = partial + ((size_t)(qa + j) * n_slabs + s) * k;
         for (int i = lane; i < k; i += 64) out[i] = L[i];
     }
+}
+
+template <int MODEL, int D>
+__global__ __launch_bounds__(kTopkWaves * 64, (D == 256 ? 1 : 2)) void topk_tiles_kernel(
+    const float* __restrict__ table, int64_t N, int64_t ld, int64_t row_base, const float* __restrict__ coef_head,
+    const float* __restrict__ coef_tail, int64_t q_head, int64_t q_tail, int q_chunk, int n_slabs, int k,
+    const FilterSpec filter, u64* __restrict__ partial) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63;
+    RowsF32<D> rows{table, N, ld, smem + wave * kSlabFloats, lane};
+    topk_tiles_run<MODEL, D>(rows, N, row_base, coef_head, coef_tail, q_head, q_tail, q_chunk, n_slabs, k, filter, partial,
+                             reinterpret_cast<u64*>(smem + kTopkWaves * kSlabFloats), wave, lane);
+}
+
+// the same over a 16-bit table (T = _Float16 / __bf16; ld in elements)
+template <int MODEL, int D, class T>
+__global__ __launch_bounds__(kTopkWaves * 64, (D == 256 ? 1 : 2)) void topk_tiles16_kernel(
+    const T* __restrict__ table, int64_t N, int64_t ld, int64_t row_base, const float* __restrict__ coef_head,
+    const float* __restrict__ coef_tail, int64_t q_head, int64_t q_tail, int q_chunk, int n_slabs, int k,
+    const FilterSpec filter, u64* __restrict__ partial) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63;
+    Rows16<D, T> rows{reinterpret_cast<const char*>(table), N, ld, smem + wave * kSlabFloats, lane};
+    topk_tiles_run<MODEL, D>(rows, N, row_base, coef_head, coef_tail, q_head, q_tail, q_chunk, n_slabs, k, filter, partial,
+                             reinterpret_cast<u64*>(smem + kTopkWaves * kSlabFloats), wave, lane);
 }
 
 // One workgroup (blockDim.x / 64 waves) per query: the k best of its n_in keys -- `keys` (Q, n_in), or made from
@@ -255,9 +348,10 @@ __global__ __launch_bounds__(kTopkMergeMaxWaves * 64) void topk_merge_kernel(con
 }
 
 // One lane per output slot: the score of the selected row by Scorer<>::score<true> from the query's own vectors
-// (LazyCoef) -- blp_score_fwd's arithmetic, bit for bit, sign of zero included.  Empty slots keep NaN.
-template <int MODEL, int D>
-__global__ __launch_bounds__(64) void topk_rescore_kernel(const float* __restrict__ table, int64_t ld, int64_t row_base,
+// (LazyCoef) -- blp_score_fwd's arithmetic, bit for bit, sign of zero included.  Empty slots keep NaN.  T: the table's
+// storage type (a 16-bit row is widened as it is read).
+template <int MODEL, int D, class T>
+__global__ __launch_bounds__(64) void topk_rescore_kernel(const T* __restrict__ table, int64_t ld, int64_t row_base,
                                                           const QRows q_fixed, const QRows q_rel, int64_t q_head, int64_t Q,
                                                           int k, const int64_t* __restrict__ rows, float* __restrict__ scores) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -266,7 +360,12 @@ __global__ __launch_bounds__(64) void topk_rescore_kernel(const float* __restric
     if (r < 0) return;
     const int64_t q = i / k;
     float e[D];
-    load_row<D>(e, table + (r - row_base) * ld);
+    const T* row = table + (r - row_base) * ld;
+#pragma unroll
+    for (int d = 0; d < D; d += 4) {
+        const float4 v = load4<T>(row + d);
+        e[d] = v.x; e[d + 1] = v.y; e[d + 2] = v.z; e[d + 3] = v.w;
+    }
     const float* f = q_fixed.row(q);
     const float* rel = q_rel.row(q);
     float s;
@@ -280,6 +379,9 @@ __global__ __launch_bounds__(64) void topk_rescore_kernel(const float* __restric
 // ------------------------------------------------------------------------------------------------ host side
 bool topk_supported(int model, int D, int k) {
     return model >= TRANSE && model <= SIMPLE && (D == 64 || D == 128 || D == 256) && k >= 1 && k <= kTopkMaxK;
+}
+bool topk_typed_supported(int model, int dtype, int D, int k) {
+    return (dtype == kTableF32 || dtype == kTableF16 || dtype == kTableBF16) && topk_supported(model, D, k);
 }
 
 struct TopkWorkspace {
@@ -327,8 +429,8 @@ hipError_t launch_topk_merge(const int64_t* rows, const float* scores, int64_t Q
     return launch_merge(nullptr, rows, scores, Q, n_in, k, rows_out, scores_out, stream);
 }
 
-template <int MODEL, int D>
-static hipError_t topk_impl(const float* table, int64_t N, int64_t ld, int64_t row_base, const QRows& q_fixed, const QRows& q_rel,
+template <int MODEL, int D, class T>
+static hipError_t topk_impl(const T* table, int64_t N, int64_t ld, int64_t row_base, const QRows& q_fixed, const QRows& q_rel,
                             int64_t q_head, int64_t q_tail, int k, const FilterSpec& filter, int64_t* rows, float* scores,
                             void* workspace, hipStream_t stream) {
     const int64_t Q = q_head + q_tail;
@@ -340,27 +442,40 @@ static hipError_t topk_impl(const float* table, int64_t N, int64_t ld, int64_t r
     const int q_chunk = topk_chunk(k);
     const int64_t n_slabs = topk_slabs(N, Q, k), n_chunks = (Q + q_chunk - 1) / q_chunk;
     const size_t lds = (size_t)kTopkWaves * kSlabFloats * 4 + (size_t)kTopkWaves * q_chunk * k * 8;
-    topk_tiles_kernel<MODEL, D><<<dim3((unsigned)(n_chunks * n_slabs)), kTopkWaves * 64, lds, stream>>>(
-        table, N, ld, row_base, w.coef_head, w.coef_tail, q_head, q_tail, q_chunk, (int)n_slabs, k, filter, w.partial);
+    const dim3 grid((unsigned)(n_chunks * n_slabs));
+    if constexpr (std::is_same<T, float>::value) {
+        topk_tiles_kernel<MODEL, D><<<grid, kTopkWaves * 64, lds, stream>>>(
+            table, N, ld, row_base, w.coef_head, w.coef_tail, q_head, q_tail, q_chunk, (int)n_slabs, k, filter, w.partial);
+    } else {
+        topk_tiles16_kernel<MODEL, D, T><<<grid, kTopkWaves * 64, lds, stream>>>(
+            table, N, ld, row_base, w.coef_head, w.coef_tail, q_head, q_tail, q_chunk, (int)n_slabs, k, filter, w.partial);
+    }
     if ((err = hipGetLastError()) != hipSuccess) return err;
     if ((err = launch_merge(w.partial, nullptr, nullptr, Q, n_slabs * k, k, rows, scores, stream)) != hipSuccess) return err;
     const int64_t slots = Q * k;
-    topk_rescore_kernel<MODEL, D><<<dim3((unsigned)((slots + 63) / 64)), 64, 0, stream>>>(table, ld, row_base, q_fixed, q_rel,
-                                                                                          q_head, Q, k, rows, scores);
+    topk_rescore_kernel<MODEL, D, T><<<dim3((unsigned)((slots + 63) / 64)), 64, 0, stream>>>(table, ld, row_base, q_fixed, q_rel,
+                                                                                             q_head, Q, k, rows, scores);
     return hipGetLastError();
 }
 
-hipError_t launch_topk(int model, int D, const float* table, int64_t N, int64_t ld, int64_t row_base, const QRows q_fixed,
+hipError_t launch_topk(int model, int D, int dtype, const void* table, int64_t N, int64_t ld, int64_t row_base, const QRows q_fixed,
                        const QRows q_rel, int64_t q_head, int64_t q_tail, int k, const FilterSpec& filter, int64_t* rows,
                        float* scores, void* workspace, hipStream_t stream) {
+#define BLP_TOPK_TYPED(M, DD, TT)                                                                                           \
+    return topk_impl<M, DD>(static_cast<const TT*>(table), N, ld, row_base, q_fixed, q_rel, q_head, q_tail, k, filter, rows, \
+                            scores, workspace, stream);
 #define BLP_TOPK_CASE(M, DD)                                                                                              \
-    if (model == M && D == DD)                                                                                            \
-        return topk_impl<M, DD>(table, N, ld, row_base, q_fixed, q_rel, q_head, q_tail, k, filter, rows, scores, workspace, \
-                                stream);
+    if (model == M && D == DD) {                                                                                          \
+        if (dtype == kTableF32) BLP_TOPK_TYPED(M, DD, float)                                                              \
+        if (dtype == kTableF16) BLP_TOPK_TYPED(M, DD, _Float16)                                                           \
+        if (dtype == kTableBF16) BLP_TOPK_TYPED(M, DD, __bf16)                                                            \
+        return hipErrorInvalidValue;                                                                                      \
+    }
 #define BLP_TOPK_MODEL(M) BLP_TOPK_CASE(M, 64) BLP_TOPK_CASE(M, 128) BLP_TOPK_CASE(M, 256)
     BLP_TOPK_MODEL(TRANSE) BLP_TOPK_MODEL(DISTMULT) BLP_TOPK_MODEL(COMPLEX) BLP_TOPK_MODEL(SIMPLE)
 #undef BLP_TOPK_MODEL
 #undef BLP_TOPK_CASE
+#undef BLP_TOPK_TYPED
     return hipErrorInvalidValue;
 }
 

@@ -345,13 +345,17 @@ def rank_all_shard(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head
     return counts
 
 
-def topk_supported(rel_model, dim, k):
-    """True if topk takes this width and k (include/blp_hip.h: blp_topk_supported -- D in {64, 128, 256}, 1 <= k <= 256)."""
-    return bool(_lib.lib().blp_topk_supported(_lib.MODEL_IDS[rel_model], int(dim), int(k)))
+def topk_supported(rel_model, dim, k, dtype=torch.float32):
+    """True if topk takes this width, k and table dtype (include/blp_hip.h: blp_topk_typed_supported -- D in {64, 128, 256},
+    1 <= k <= 256, a float32, float16 or bfloat16 table)."""
+    if dtype not in TABLE_DTYPES:
+        return False
+    return bool(_lib.lib().blp_topk_typed_supported(_lib.MODEL_IDS[rel_model], TABLE_DTYPES[dtype], int(dim), int(k)))
 
 
-def topk_workspace_bytes(rel_model, N, D, q_head, q_tail, k):
-    return int(_lib.lib().blp_topk_workspace_bytes(_lib.MODEL_IDS[rel_model], int(N), int(D), int(q_head), int(q_tail), int(k)))
+def topk_workspace_bytes(rel_model, N, D, q_head, q_tail, k, dtype=torch.float32):
+    return int(_lib.lib().blp_topk_typed_workspace_bytes(_lib.MODEL_IDS[rel_model], TABLE_DTYPES[dtype], int(N), int(D), int(q_head),
+                                                         int(q_tail), int(k)))
 
 
 def topk(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, filter=None, row_base=0, out=None):
@@ -360,10 +364,15 @@ def topk(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, filte
     global rows [row_base, row_base + N), with the highest score_fn value, as blp_topk orders them (descending score, ties by
     ascending row, NaN last; numpy's argsort(-scores, kind="stable")[:k]).  ``filter``: a SegmentFilter whose row_base is
     ``row_base``; the rows it names are removed.  Slots beyond the candidates left: row -1, score NaN.
+    ``table`` may be float16 / bfloat16 (blp_topk_typed: the result is the float32 table's, widened exactly, read at half the
+    bytes); ``source`` and ``rel_emb`` are float32.
     Returns (rows (Q, k) int64, scores (Q, k) float32); ``out`` may give both."""
     _require_device(table, source, fixed_row, rel_emb, rel_ids)
-    table = _f32_rows(table, "table")
-    source = table if source is table else _f32_rows(source, "source")
+    if source is table and table.dtype != torch.float32:
+        raise TypeError("a 16-bit table needs a float32 `source` for the queries' vectors (ops.gather_triple_vectors + build_queries(by_position=True))")
+    same = source is table
+    table = _table_rows(table, "table")
+    source = table if same else _f32_rows(source, "source")
     rel_emb = _f32_rows(rel_emb, "rel_emb").contiguous()
     N, D = table.shape
     if source.dim() != 2 or source.shape[1] != D:
@@ -375,7 +384,7 @@ def topk(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, filte
         raise ValueError("fixed_row and rel_ids need one entry per query; rel_emb must be (R, D)")
     if not 0 <= q_head <= Q:
         raise ValueError(f"q_head = {q_head} outside [0, {Q}]")
-    if not topk_supported(rel_model, D, k):
+    if not topk_supported(rel_model, D, k, table.dtype):
         raise ValueError(f"topk: D = {D}, k = {k} not supported (D in 64 / 128 / 256, 1 <= k <= 256): see topk_supported")
     if filter is not None and int(filter.row_base) != int(row_base):
         raise ValueError(f"topk: the filter's row_base {filter.row_base} differs from row_base {row_base}")
@@ -390,16 +399,17 @@ def topk(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, filte
         return rows, scores
     L = _lib.lib()
     model = _lib.MODEL_IDS[rel_model]
-    ws_bytes = L.blp_topk_workspace_bytes(model, N, D, q_head, Q - q_head, k)
+    tdt = TABLE_DTYPES[table.dtype]
+    ws_bytes = L.blp_topk_typed_workspace_bytes(model, tdt, N, D, q_head, Q - q_head, k)
     stream = torch._C._cuda_getCurrentRawStream(dev.index)
     workspace = _workspace(dev, stream, ws_bytes)
     spec = None if filter is None else _filter_spec(filter, Q, dev)
-    status = L.blp_topk(model, table.data_ptr(), N, D, table.stride(0) if N > 1 else D, int(row_base), source.data_ptr(),
-                        source.shape[0], source.stride(0) if source.shape[0] > 1 else D, fixed_row.data_ptr(), rel_emb.data_ptr(),
-                        rel_emb.shape[0], rel_ids.data_ptr(), q_head, Q - q_head, k, spec, rows.data_ptr(), scores.data_ptr(),
-                        workspace.data_ptr(), ws_bytes, dev.index, stream)
+    status = L.blp_topk_typed(model, table.data_ptr(), tdt, N, D, table.stride(0) if tdt or N > 1 else D, int(row_base),
+                              source.data_ptr(), source.shape[0], source.stride(0) if source.shape[0] > 1 else D, fixed_row.data_ptr(),
+                              rel_emb.data_ptr(), rel_emb.shape[0], rel_ids.data_ptr(), q_head, Q - q_head, k, spec, rows.data_ptr(),
+                              scores.data_ptr(), workspace.data_ptr(), ws_bytes, dev.index, stream)
     if status:
-        _lib.check(status, "blp_topk")
+        _lib.check(status, "blp_topk_typed" if tdt else "blp_topk")
     return rows, scores
 
 

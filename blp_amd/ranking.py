@@ -544,7 +544,8 @@ def predict_links(model, table, triples, k, ent2idx, *, side="both", filter_inde
     Returns (rows or ids (Q, k) int64, scores (Q, k) float32): descending score, ties by ascending row, NaN last; -1 / NaN
     beyond the candidates left.  Scores are score_fn's values bit for bit.  HIP tensors at a width blp_topk takes: blp_topk
     (one call per rank; shards merged by one all-gather of the (Q, k) lists + blp_topk_merge); otherwise the reference's
-    dense route (score_fn + a stable sort) in query chunks."""
+    dense route (score_fn + a stable sort) in query chunks.  A float16 / bfloat16 HIP table takes blp_topk_typed, which reads
+    the 16-bit rows as they are: rows and scores are those of the same table widened to float32, bit for bit."""
     model = _module(model)
     if side not in ("head", "tail", "both"):
         raise ValueError(f"side must be 'head', 'tail' or 'both', got {side!r}")
@@ -579,13 +580,17 @@ def predict_links(model, table, triples, k, ent2idx, *, side="both", filter_inde
         source, src_rows = fixed_vecs, torch.arange(Q, device=device)
     else:
         source, src_rows = table, fixed_rows
+    fused = table.is_cuda and ops.topk_supported(model.rel_model, D, k, table.dtype)
+    if fused and table.dtype != torch.float32:
+        # the kernels take float32 query vectors: the Q fixed rows, widened (exact; after the sum on several ranks -- x + 0
+        # is exact in 16 bits too)
+        source, src_rows = (source if world > 1 else table[fixed_rows]).float(), torch.arange(Q, device=device)
     filt = None
     if filter_index is not None and Q:
         seg = filter_index.segments(triples, ent2idx, device, row_base=row_lo)
         sel = torch.cat([x for x, on in ((torch.arange(T, device=device), heads), (torch.arange(T, 2 * T, device=device), tails)) if on])
         filt = ops.SegmentFilter(seg.seg_lo[sel].contiguous(), seg.seg_hi[sel].contiguous(), seg.values,
                                  seg.exclude[sel].contiguous(), seg.ent2idx, row_lo)
-    fused = table.is_cuda and table.dtype == torch.float32 and ops.topk_supported(model.rel_model, D, k)
     if fused:
         rows, scores = ops.topk(model.rel_model, table, source, src_rows, rel_w, rel_ids, q_head, k, filter=filt, row_base=row_lo)
     else:

@@ -484,6 +484,20 @@ int blp_topk(int model, const float *table, int64_t N, int D, int64_t ld, int64_
  * out as the quiet NaN 0x7fc00000).  The second stage of blp_topk, on caller-given lists; no workspace. */
 int blp_topk_merge(const int64_t *rows, const float *scores, int64_t Q, int lists, int k_in, int k, int64_t *rows_out,
                    float *scores_out, int device, void *stream);
+/* blp_topk over a candidate table in any storage type (table_dtype: BLP_DTYPE_*; see "THE CANDIDATE TABLE MAY COME IN A 16-BIT
+ * STORAGE TYPE" above): the same contract on the table WIDENED to f32 exactly -- the same rows in the same order, the
+ * reference's f32 scores of the widened rows bit for bit (sign of zero included), filtered rows removed, -1 / NaN slots, the
+ * same workspace (it does not depend on the storage type), independent of the grid.  A 16-bit table's row stride ld is in
+ * ELEMENTS, ld % 8 == 0, 16-byte aligned base; source and rel_emb stay f32 (the queries' vectors: gather and widen the
+ * fixed entities' rows, blp_gather_triple_vectors).  BLP_DTYPE_F32 is blp_topk itself.  An unknown table_dtype is
+ * BLP_ERR_BAD_ARG (the _supported / _workspace_bytes calls answer 0).  The 16-bit rows are read as they are: half the bytes of
+ * the f32 table per pass. */
+int blp_topk_typed_supported(int model, int table_dtype, int D, int k);
+size_t blp_topk_typed_workspace_bytes(int model, int table_dtype, int64_t N, int D, int64_t q_head, int64_t q_tail, int k);
+int blp_topk_typed(int model, const void *table, int table_dtype, int64_t N, int D, int64_t ld, int64_t row_base,
+                   const float *source, int64_t S, int64_t ld_src, const int64_t *fixed_row, const float *rel_emb, int64_t R,
+                   const int64_t *rel_id, int64_t q_head, int64_t q_tail, int k, const blp_filter *filter, int64_t *rows,
+                   float *scores, void *workspace, size_t workspace_bytes, int device, void *stream);
 
 /* --------------------------------------------------------------------------------------------
  * Re-ranking a first-stage retrieval run (reference retrieval.py rerank: BM25F candidates of DBpedia-Entity v2 re-scored

@@ -10,6 +10,12 @@ device events; warm-up, then --steps steps; one JSON line with the median and p9
                                 build, rank_kernel = 1; both calls on the hooks build)
   fb15k237-transe-128q          128 queries of the same table, k = 10                vs blp_rank_all_shard (default route)
   fb15k237-transe-ties5pct      the ties5pct table (5 % of the rows per cluster centre), k = 10 vs the random table's top-k
+
+    python tools/topk_bench.py --table16 {float16,bfloat16} [...]
+
+  the same workloads with the table rounded to the 16-bit type: blp_topk_typed on the 16-bit copy, timed alternately against
+  blp_topk on the same values widened to float32 (the queries' vectors are the widened rows in both calls); the ties5pct
+  workload is not run.
 """
 import argparse
 import json
@@ -103,13 +109,58 @@ def run(name, label, p, k, steps, warmup, against="rank", hooks_exact=False, oth
     return res
 
 
+def run16(label, p, k, steps, warmup, dtype):
+    model = p["cfg"]["model"]
+    t16 = p["table"].to(dtype)
+    wide = t16.float()
+    del p["table"]
+    torch.cuda.empty_cache()
+    N, D = t16.shape
+    Q = p["fixed"].shape[0]
+    args = (p["fixed"], p["rel"], p["rel_ids"], p["q_head"], k)
+    calls = {"topk16": lambda: ops.topk(model, t16, wide, *args, filter=p["filter"]),
+             "topk": lambda: ops.topk(model, wide, wide, *args, filter=p["filter"])}
+    a, b = calls["topk16"](), calls["topk"]()
+    same = torch.equal(a[0], b[0]) and torch.equal(a[1].view(torch.int32), b[1].view(torch.int32))
+    ms = measure(calls, steps, warmup)
+    res = {"workload": label, "table": str(dtype).replace("torch.", ""), "model": model, "N": N, "D": D, "Q": Q, "k": k,
+           "filtered": True, "steps": steps, "warmup": warmup, "same_as_f32": same}
+    for n, v in ms.items():
+        res[f"{n}_ms"] = stats(v)
+    res["ratio_median"] = round(res["topk16_ms"]["median"] / res["topk_ms"]["median"], 3)
+    tk = res["topk16_ms"]["median"] * 1e-3
+    res["hbm_tbs"] = round(N * D * 2 / tk / 1e12, 3)
+    res["hbm_frac"] = round(res["hbm_tbs"] / HBM_TBS, 3)
+    print(json.dumps(res), flush=True)
+    return res
+
+
+def main16(a):
+    dtype = getattr(torch, a.table16)
+    want = lambda n: a.only is None or n in a.only
+    for model in ("transe", "complex"):
+        label = f"wikidata5m-{model}"
+        if want(label):
+            run16(label, problem(label, triples=2), a.k, a.steps, a.warmup, dtype)
+            torch.cuda.empty_cache()
+    for model in ("transe", "distmult"):
+        label = f"fb15k237-{model}"
+        if want(label):
+            run16(label, problem(label), a.k, a.steps, a.warmup, dtype)
+    if want("fb15k237-transe-128q"):
+        run16("fb15k237-transe-128q", problem("fb15k237-transe", triples=64), a.k, a.steps, a.warmup, dtype)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--only", nargs="*", default=None)
+    ap.add_argument("--table16", choices=("float16", "bfloat16"), default=None)
     a = ap.parse_args()
+    if a.table16:
+        return main16(a)
     want = lambda n: a.only is None or n in a.only
     for model in ("transe", "complex"):
         label = f"wikidata5m-{model}"
