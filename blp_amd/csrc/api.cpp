@@ -756,6 +756,73 @@ int blp_topk_merge(const int64_t* rows, const float* scores, int64_t Q, int list
     return BLP_OK;
 }
 
+// ---- per-query candidate lists (rank_lists.hip)
+int blp_rank_lists_supported(int model, int table_dtype, int D) {
+    return valid_model(model) && blp::rank_lists_supported(model, table_dtype, D) ? 1 : 0;
+}
+
+size_t blp_rank_lists_workspace_bytes(int model, int table_dtype, int D, int64_t q_head, int64_t q_tail) {
+    if (!blp_rank_lists_supported(model, table_dtype, D) || q_head < 0 || q_tail < 0) return 0;
+    return blp::rank_lists_workspace_bytes(q_head, q_tail);
+}
+
+int blp_rank_lists(int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld, int64_t row_base, const float* source,
+                   int64_t S, int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R, const int64_t* rel_id,
+                   const int64_t* true_row, int64_t q_head, int64_t q_tail, const int64_t* list_ptr, const int64_t* list_row,
+                   int64_t nnz, const blp_filter* filter, int32_t* counts, float* scores, void* workspace, size_t workspace_bytes,
+                   int device, void* stream) {
+    const char* who = "blp_rank_lists";
+    if (!valid_model(model)) return fail(BLP_ERR_BAD_ARG, "%s: unknown model %d", who, model);
+    if (!valid_table_dtype(table_dtype)) return fail(BLP_ERR_BAD_ARG, "%s: unknown table dtype %d", who, table_dtype);
+    if (!blp_rank_lists_supported(model, table_dtype, D))
+        return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (TransE: D %% 4 == 0 up to 1024; the other models: 64 / 128 / "
+                                             "256: see blp_rank_lists_supported)", who, D);
+    if (N < 0 || q_head < 0 || q_tail < 0 || ld < D || row_base < 0 || nnz < 0)
+        return fail(BLP_ERR_BAD_ARG, "%s: negative size / row_base or ld < D (N=%lld q_head=%lld q_tail=%lld ld=%lld nnz=%lld)", who,
+                    (long long)N, (long long)q_head, (long long)q_tail, (long long)ld, (long long)nnz);
+    if (nnz >= (1ll << 31)) return fail(BLP_ERR_BAD_ARG, "%s: nnz = %lld list entries, at most 2^31 - 1 (counts are int32)", who, (long long)nnz);
+    if (row_base + N > (1ll << 31) || q_head + q_tail > (1ll << 30))
+        return fail(BLP_ERR_BAD_ARG, "%s: global rows must stay below 2^31 and Q below 2^30", who);
+    if (!counts && !scores) return fail(BLP_ERR_BAD_ARG, "%s: both outputs NULL (give counts, scores or both)", who);
+    if ((counts == nullptr) != (true_row == nullptr))
+        return fail(BLP_ERR_BAD_ARG, "%s: counts and true_row go together (counts are taken against the true entity's score)", who);
+    const int64_t Q = q_head + q_tail;
+    if (Q > 0 && (!source || !fixed_row || !rel_id || !rel_emb || !list_ptr || R <= 0 || S <= 0))
+        return fail(BLP_ERR_BAD_ARG, "%s: NULL source / fixed_row / rel_id / rel_emb / list_ptr, or R <= 0 / S <= 0", who);
+    if (nnz > 0 && (Q == 0 || !list_row)) return fail(BLP_ERR_BAD_ARG, "%s: %lld list entries but no query, or NULL list_row", who, (long long)nnz);
+    if (N > 0 && !table) return fail(BLP_ERR_BAD_ARG, "%s: NULL table", who);
+    if (!table_rows_aligned(table, table_dtype, ld) || !aligned16(source) || (ld_src & 3) || ld_src < D || !aligned16(rel_emb) ||
+        !aligned16(counts))
+        return fail(BLP_ERR_BAD_ARG, table_dtype == BLP_DTYPE_F32
+                                         ? "%s: table / source / rel_emb / counts must be 16-byte aligned, ld %% 4 == 0, ld_src %% 4 == 0, ld_src >= D"
+                                         : "%s: table / source / rel_emb / counts must be 16-byte aligned, ld %% 8 == 0 (a 16-bit table's row "
+                                           "stride, in elements), ld_src %% 4 == 0, ld_src >= D",
+                    who);
+    blp::FilterSpec spec;
+    if (filter) {
+        if (!filter->seg_lo || !filter->seg_hi || !filter->values || (filter->ent2idx && filter->ent2idx_len < 0))
+            return fail(BLP_ERR_BAD_ARG, "%s: filter needs seg_lo, seg_hi and values (ent2idx_len >= 0)", who);
+        if (filter->row_base != row_base)
+            return fail(BLP_ERR_BAD_ARG, "%s: filter row_base %lld differs from the call's row_base %lld", who,
+                        (long long)filter->row_base, (long long)row_base);
+        spec.lo = filter->seg_lo; spec.hi = filter->seg_hi; spec.val = filter->values; spec.exclude = filter->exclude;
+        spec.ent2idx = filter->ent2idx; spec.ent2idx_len = filter->ent2idx ? filter->ent2idx_len : 0;
+        spec.row_base = filter->row_base;
+    }
+    if (Q == 0) return BLP_OK;
+    const size_t need = counts ? blp::rank_lists_workspace_bytes(q_head, q_tail) : 0;
+    if (need && (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255u)))
+        return fail(BLP_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned and >= %zu bytes (got %zu)", who, need, workspace_bytes);
+    DeviceGuard guard(device);
+    if (guard.error() != hipSuccess) return hip_fail(guard.error(), "hipSetDevice");
+    const blp::QRows truth = true_row ? blp::QRows::rows_of(source, true_row, ld_src) : blp::QRows();
+    hipError_t err = blp::launch_rank_lists(model, D, table_dtype, table, N, ld, row_base, blp::QRows::rows_of(source, fixed_row, ld_src),
+                                            blp::QRows::rows_of(rel_emb, rel_id, D), truth, q_head, q_tail, list_ptr, list_row, nnz, spec,
+                                            counts, scores, workspace, static_cast<hipStream_t>(stream));
+    if (err != hipSuccess) return hip_fail(err, "blp_rank_lists launch");
+    return BLP_OK;
+}
+
 // ---- re-ranking a retrieval run (rerank.hip)
 static_assert(BLP_RERANK_MAX_SEGMENT == blp::kRerankMaxSegment && BLP_RERANK_MAX_CUTOFFS == blp::kRerankMaxCutoffs,
               "include/blp_hip.h and launch.h disagree on the re-ranking limits");

@@ -97,12 +97,13 @@ __device__ __forceinline__ float transe_key_64(const TE* pe, const float* pf, co
 // The same at a run-time width D (D % 4 == 0; the bag-of-words / DKRL widths 300, 768), straight from the entity and
 // relation vectors: head-replacing query (e + r) - f with f = the tail, tail-replacing (f + r) - e with f = the head
 // (models.py:222-223).  The last chunk of a width that is not a multiple of 32 loads only the columns that exist.
-__device__ __forceinline__ void gather_issue_rt(float (&x)[32], const float* const (&g)[8], int s, int cols, int lane) {
+template <class TE = float>
+__device__ __forceinline__ void gather_issue_rt(float (&x)[32], const TE* const (&g)[8], int s, int cols, int lane) {
     const bool mine = (lane & 7) * 4 < cols;  // cols is a multiple of 4: a lane's four columns exist together
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (mine) v = *reinterpret_cast<const float4*>(g[i] + 32 * s);
+        if (mine) v = load4<TE>(g[i] + 32 * s);  // (a 16-bit row: widened here, exactly)
         x[4 * i] = v.x; x[4 * i + 1] = v.y; x[4 * i + 2] = v.z; x[4 * i + 3] = v.w;
     }
 }
@@ -176,10 +177,11 @@ __device__ __forceinline__ void stage_query_rt(const float* __restrict__ f, cons
     }
 }
 
-__device__ __forceinline__ float transe_key_64_one_query_rt(const float* pe, const float* qa, const float* qb, int D, bool head,
+template <class TE = float>  // TE: the candidate rows' storage type (rank_lists.hip gathers 16-bit rows through it)
+__device__ __forceinline__ float transe_key_64_one_query_rt(const TE* pe, const float* qa, const float* qb, int D, bool head,
                                                             float* slab, int lane) {
     const int sub_row = lane >> 3, sub_col = (lane & 7) * 4;
-    const float* ge[8];
+    const TE* ge[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) ge[k] = shfl_ptr(pe, 8 * k + sub_row) + sub_col;
     float sum = 0.0f;

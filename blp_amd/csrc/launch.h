@@ -99,6 +99,15 @@ hipError_t launch_topk(int model, int D, int dtype, const void* table, int64_t N
 hipError_t launch_topk_merge(const int64_t* rows, const float* scores, int64_t Q, int64_t n_in, int k, int64_t* rows_out,
                              float* scores_out, hipStream_t stream);
 
+// rank_lists.hip: counts and scores of per-query candidate lists (include/blp_hip.h: blp_rank_lists); q_true.base == nullptr
+// with counts == nullptr: scores only.  The workspace holds the true keys (needed with counts only).
+bool rank_lists_supported(int model, int dtype, int D);
+size_t rank_lists_workspace_bytes(int64_t q_head, int64_t q_tail);
+hipError_t launch_rank_lists(int model, int D, int dtype, const void* table, int64_t N, int64_t ld, int64_t row_base,
+                             const QRows q_fixed, const QRows q_rel, const QRows q_true, int64_t q_head, int64_t q_tail,
+                             const int64_t* list_ptr, const int64_t* list_row, int64_t nnz, const FilterSpec& filter, int32_t* counts,
+                             float* scores, void* workspace, hipStream_t stream);
+
 // rerank.hip: re-ranking a retrieval run (include/blp_hip.h: blp_rerank_cosine, blp_rerank_ndcg)
 constexpr int kRerankMaxSegment = 8192;  // candidates per query: 8 192 keys of 8 bytes = 64 KiB of LDS
 constexpr int kRerankMaxCutoffs = 8;

@@ -4,6 +4,7 @@ device memory and the stream; every arithmetic step of the hot path runs in the 
     rank_all(...)       all-entities ranking counts        (train.py:146-171, utils.py:103-105)
     rank_metrics(...)   counts -> reciprocal ranks, hits   (utils.py:104-109)
     topk(...)           filtered top-k prediction per query (no score matrix)
+    rank_lists(...)     counts / scores of per-query candidate lists (only the listed rows are read)
     rerank_cosine(...)  cosine of every retrieval candidate with its query (retrieval.py:170-175)
     rerank_ndcg(...)    trec_eval ndcg_cut of every (alpha, query) of a re-ranked run (retrieval.py:139-258)
     score(...)          score_fn(heads, tails, rels)       (models.py:222-248), differentiable
@@ -411,6 +412,84 @@ def topk(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, filte
     if status:
         _lib.check(status, "blp_topk_typed" if tdt else "blp_topk")
     return rows, scores
+
+
+def rank_lists_supported(rel_model, dim, dtype=torch.float32):
+    """True if rank_lists takes this width and table dtype (include/blp_hip.h: blp_rank_lists_supported -- TransE at any
+    D % 4 == 0 up to 1024, the other models at 64 / 128 / 256; a float32, float16 or bfloat16 table)."""
+    if dtype not in TABLE_DTYPES:
+        return False
+    return bool(_lib.lib().blp_rank_lists_supported(_lib.MODEL_IDS[rel_model], TABLE_DTYPES[dtype], int(dim)))
+
+
+def rank_lists(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, list_ptr, list_row, true_row=None, filter=None,
+               row_base=0, want_scores=False, out=None):
+    """Counts and / or scores of per-query candidate lists (blp_rank_lists).  Queries as in rank_all_shard -- head-replacing
+    [0, q_head), then tail-replacing; fixed_row / true_row (Q,) index ``source`` (S, D) float32, rel_ids (Q,) index ``rel_emb``
+    (R, D).  Query q owns entries [list_ptr[q], list_ptr[q + 1]) of ``list_row`` (nnz,) int64 GLOBAL rows of ``table`` (N, D)
+    (float32 / float16 / bfloat16), which holds global rows [row_base, row_base + N); entries outside (-1 padding, another
+    shard's rows) are skipped: counted nowhere, score NaN.  list_ptr (Q + 1,) must be non-decreasing from 0 to nnz.
+    ``true_row`` given: counts (Q, 4) int32 {gt, ge, gt_filtered, ge_filtered} of the list's entries against the true entity's
+    score (a multiset: duplicates count; ``filter``: a SegmentFilter whose row_base is ``row_base``).  ``want_scores`` (or no
+    true_row): scores (nnz,) float32, score_fn's values bit for bit.  Returns (counts or None, scores or None); ``out`` may
+    give both (None for the one not wanted)."""
+    _require_device(table, source, fixed_row, rel_emb, rel_ids, list_ptr, list_row, true_row)
+    if source is table and table.dtype != torch.float32:
+        raise TypeError("a 16-bit table needs a float32 `source` for the queries' vectors")
+    same = source is table
+    table = _table_rows(table, "table")
+    source = table if same else _f32_rows(source, "source")
+    rel_emb = _f32_rows(rel_emb, "rel_emb").contiguous()
+    N, D = table.shape
+    if source.dim() != 2 or source.shape[1] != D:
+        raise ValueError(f"source must be (S, {D}), got {tuple(source.shape)}")
+    fixed_row, rel_ids, list_ptr, list_row = _i64_vector(fixed_row), _i64_vector(rel_ids), _i64_vector(list_ptr), _i64_vector(list_row)
+    Q, nnz = fixed_row.shape[0], list_row.shape[0]
+    if rel_ids.shape[0] != Q or list_ptr.shape[0] != Q + 1 or rel_emb.dim() != 2 or rel_emb.shape[1] != D:
+        raise ValueError("fixed_row and rel_ids need one entry per query, list_ptr Q + 1; rel_emb must be (R, D)")
+    if not 0 <= q_head <= Q:
+        raise ValueError(f"q_head = {q_head} outside [0, {Q}]")
+    if not rank_lists_supported(rel_model, D, table.dtype):
+        raise ValueError(f"rank_lists: D = {D} not supported for {rel_model} (see rank_lists_supported)")
+    if filter is not None and int(filter.row_base) != int(row_base):
+        raise ValueError(f"rank_lists: the filter's row_base {filter.row_base} differs from row_base {row_base}")
+    want_scores = bool(want_scores) or true_row is None
+    dev = table.device
+    counts, scores = out if out is not None else (None, None)
+    if true_row is not None:
+        true_row = _i64_vector(true_row)
+        if true_row.shape[0] != Q:
+            raise ValueError("true_row needs one entry per query")
+        if counts is None:
+            counts = torch.empty((Q, 4), dtype=torch.int32, device=dev)
+        if counts.shape != (Q, 4) or counts.dtype != torch.int32 or not counts.is_contiguous():
+            raise ValueError("out[0] must be a contiguous (Q, 4) int32 tensor")
+    else:
+        counts = None
+    if want_scores:
+        if scores is None:
+            scores = torch.empty((nnz,), dtype=torch.float32, device=dev)
+        if scores.shape != (nnz,) or scores.dtype != torch.float32 or not scores.is_contiguous():
+            raise ValueError("out[1] must be a contiguous (nnz,) float32 tensor")
+    else:
+        scores = None
+    if Q == 0:
+        return counts, scores
+    L = _lib.lib()
+    model = _lib.MODEL_IDS[rel_model]
+    tdt = TABLE_DTYPES[table.dtype]
+    stream = torch._C._cuda_getCurrentRawStream(dev.index)
+    ws_bytes = L.blp_rank_lists_workspace_bytes(model, tdt, D, q_head, Q - q_head) if counts is not None else 0
+    workspace = _workspace(dev, stream, ws_bytes) if ws_bytes else None
+    spec = None if filter is None else _filter_spec(filter, Q, dev)
+    status = L.blp_rank_lists(model, table.data_ptr(), tdt, N, D, table.stride(0) if tdt or N > 1 else D, int(row_base),
+                              source.data_ptr(), source.shape[0], source.stride(0) if source.shape[0] > 1 else D, fixed_row.data_ptr(),
+                              rel_emb.data_ptr(), rel_emb.shape[0], rel_ids.data_ptr(), _addr(true_row), q_head, Q - q_head,
+                              list_ptr.data_ptr(), list_row.data_ptr(), nnz, spec, _addr(counts), _addr(scores), _addr(workspace),
+                              ws_bytes, dev.index, stream)
+    if status:
+        _lib.check(status, "blp_rank_lists")
+    return counts, scores
 
 
 def topk_merge(rows, scores, k):

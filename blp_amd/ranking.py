@@ -491,6 +491,30 @@ def _stable_topk(scores, rows, removed, k):
     return out_rows, out_scores
 
 
+def _filtered_pairs(filt, lo, hi, row_base, N, dev):
+    """What the filter removes for queries [lo, hi): (owner, local) -- query lo + owner loses table row local -- from the
+    segments (seg_lo, seg_hi, values, exclude, ent2idx) as SegmentFilter holds them (None: nothing), with blp_filter's
+    semantics: exclude[q] is never removed, ids without a row and rows outside [row_base, row_base + N) remove nothing."""
+    none = torch.empty(0, dtype=torch.int64, device=dev)
+    if filt is None:
+        return none, none
+    seg_lo, seg_hi, values, exclude, e2i = filt
+    n_per = (seg_hi[lo:hi] - seg_lo[lo:hi]).clamp(min=0)
+    total = int(n_per.sum())
+    if not total:
+        return none, none
+    owner = torch.repeat_interleave(torch.arange(hi - lo, device=dev), n_per, output_size=total)
+    first = torch.cumsum(n_per, 0) - n_per
+    vals = values[seg_lo[lo:hi][owner] + torch.arange(total, device=dev) - first[owner]]
+    keep = torch.ones_like(vals, dtype=torch.bool) if exclude is None else vals != exclude[lo:hi][owner]
+    if e2i is not None:
+        ok = (vals >= 0) & (vals < e2i.shape[0])
+        vals = torch.where(ok, e2i[torch.where(ok, vals, torch.zeros_like(vals))], torch.full_like(vals, -1))
+    local = vals - row_base
+    keep &= (local >= 0) & (local < N)
+    return owner[keep], local[keep]
+
+
 def _topk_dense(score_fn, table, fixed, rel, q_head, k, row_base, filt, max_matrix_bytes=1 << 28):
     """The reference's route (score_fn over the whole table, train.py:146-147) + the stable order, in query chunks of a
     bounded (chunk, N) matrix: CPU tensors, and widths blp_topk is not compiled for.  filt: (seg_lo, seg_hi, values,
@@ -511,21 +535,8 @@ def _topk_dense(score_fn, table, fixed, rel, q_head, k, row_base, filt, max_matr
                 parts.append(score_fn(ent, f, r) if head else score_fn(f, ent, r))
         pred = torch.cat(parts) if len(parts) > 1 else parts[0]
         removed = torch.zeros(pred.shape, dtype=torch.bool, device=dev)
-        if filt is not None:
-            seg_lo, seg_hi, values, exclude, e2i = filt
-            n_per = (seg_hi[lo:hi] - seg_lo[lo:hi]).clamp(min=0)
-            total = int(n_per.sum())
-            if total:
-                owner = torch.repeat_interleave(torch.arange(hi - lo, device=dev), n_per, output_size=total)
-                first = torch.cumsum(n_per, 0) - n_per
-                vals = values[seg_lo[lo:hi][owner] + torch.arange(total, device=dev) - first[owner]]
-                keep = torch.ones_like(vals, dtype=torch.bool) if exclude is None else vals != exclude[lo:hi][owner]
-                if e2i is not None:
-                    ok = (vals >= 0) & (vals < e2i.shape[0])
-                    vals = torch.where(ok, e2i[torch.where(ok, vals, torch.zeros_like(vals))], torch.full_like(vals, -1))
-                local = vals - row_base
-                keep &= (local >= 0) & (local < N)
-                removed[owner[keep], local[keep]] = True
+        owner, local = _filtered_pairs(filt, lo, hi, row_base, N, dev)
+        removed[owner, local] = True
         rows_out[lo:hi], scores_out[lo:hi] = _stable_topk(pred, grows.expand(hi - lo, N), removed, k)
     return rows_out, scores_out
 
@@ -612,6 +623,147 @@ def predict_links(model, table, triples, k, ent2idx, *, side="both", filter_inde
         entities = entities.to(device=device, dtype=torch.long)
         rows = torch.where(rows >= 0, entities[rows.clamp(min=0)], rows)
     return rows, scores
+
+
+# ----------------------------------------------------------------------------------- per-query candidate lists
+def sample_candidates(num_queries, num_rows, c, generator=None, device=None):
+    """(num_queries, c) int64 table rows drawn uniformly (with replacement) from [0, num_rows) by a torch generator: the
+    deterministic helper of a sampled-candidate evaluation (rank_candidates(..., include_true=False)).  The reference has no
+    such protocol; this only fixes how the negatives are drawn."""
+    where = generator.device if generator is not None else "cpu"
+    rows = torch.randint(0, int(num_rows), (int(num_queries), int(c)), generator=generator, device=where, dtype=torch.int64)
+    return rows if device is None else rows.to(device)
+
+
+def _rank_lists_dense(score_fn, table, fixed, rel, true_vec, q_head, ptr, rows, row_base, filt, want_scores,
+                      max_bytes=1 << 28):
+    """The dense route of rank_candidates: score_fn on the gathered rows of the lists, in query chunks of bounded bytes, the
+    comparisons against the true score, the filter through _filtered_pairs.  CPU tensors and widths blp_rank_lists does not
+    take; on CPU tensors it is the oracle of the fused route.  fixed / rel / true_vec: (Q, D) float32 (true_vec None: scores
+    only); ptr (Q + 1,), rows (nnz,) global rows.  Returns (counts (Q, 4) int32 or None, scores (nnz,) or None)."""
+    Q, (N, D) = fixed.shape[0], table.shape
+    dev = table.device
+    nnz = rows.shape[0]
+    counts = torch.zeros((Q, 4), dtype=torch.int32, device=dev) if true_vec is not None else None
+    scores = torch.full((nnz,), float("nan"), dtype=torch.float32, device=dev) if want_scores else None
+    budget = max(1, max_bytes // (12 * D))  # entries per chunk: three gathered (n, D) float32 operands
+    ptr_host = ptr.tolist()
+    lo = 0
+    while lo < Q:
+        hi = lo + 1
+        while hi < Q and ptr_host[hi + 1] - ptr_host[lo] <= budget:
+            hi += 1
+        p0, p1 = ptr_host[lo], ptr_host[hi]
+        n_per = ptr[lo + 1:hi + 1] - ptr[lo:hi]
+        owner = torch.repeat_interleave(torch.arange(hi - lo, device=dev), n_per, output_size=p1 - p0)
+        local = rows[p0:p1] - row_base
+        valid = (local >= 0) & (local < N)
+        e = table[torch.where(valid, local, torch.zeros_like(local))].float() if N else table.new_zeros((p1 - p0, D)).float()
+        f, r = fixed[lo:hi][owner], rel[lo:hi][owner]
+        is_head = owner < q_head - lo
+        s = torch.empty((p1 - p0,), dtype=torch.float32, device=dev)
+        if bool(is_head.any()):
+            s[is_head] = score_fn(e[is_head], f[is_head], r[is_head])
+        if bool((~is_head).any()):
+            s[~is_head] = score_fn(f[~is_head], e[~is_head], r[~is_head])
+        if scores is not None:
+            scores[p0:p1] = torch.where(valid, s, torch.full_like(s, float("nan")))
+        if counts is not None:
+            h_end = max(min(hi, q_head) - lo, 0)
+            tv, fq, rq = true_vec[lo:hi], fixed[lo:hi], rel[lo:hi]
+            true = torch.cat((score_fn(tv[:h_end], fq[:h_end], rq[:h_end]), score_fn(fq[h_end:], tv[h_end:], rq[h_end:])))
+            kt = true[owner]
+            gt, ge = valid & (s > kt), valid & (s >= kt)
+            f_owner, f_local = _filtered_pairs(filt, lo, hi, row_base, N, dev)
+            span = max(N, 1)
+            kept = ~torch.isin(owner * span + torch.where(valid, local, torch.zeros_like(local)), f_owner * span + f_local)
+            for col, mask in enumerate((gt, ge, gt & kept, ge & kept)):
+                counts[lo:hi, col] = torch.zeros(hi - lo, dtype=torch.int64, device=dev).index_add_(0, owner, mask.to(torch.int64)).to(torch.int32)
+        lo = hi
+    return counts, scores
+
+
+def rank_candidates(model, table, triples, candidates, ent2idx, *, side="both", filter_index=None, candidates_are="rows",
+                    include_true=True, return_scores=False):
+    """Rank every triple's true entity against a candidate list of its own -- sampled negatives, the candidates of a first
+    stage to re-rank -- instead of the whole table: only the listed rows are read.
+    triples      (T, 3) (head, tail, rel); ``side`` "head": (?, r, t); "tail": (h, r, ?); "both": Q = 2 T queries in
+                 predict_links' order [heads | tails]
+    candidates   (Q, C) int64, padded with -1, or a CSR pair (ptr (Q + 1,), rows (nnz,)); table rows, or entity ids mapped
+                 through ``ent2idx`` with candidates_are="ids" (an id without a row is skipped).  A list is a multiset
+    ent2idx      utils.make_ent2idx map (entity id -> table row); the fixed and the true entity of a query must have a row
+    filter_index utils.FilterIndex of the known edges: the filtered columns count only entries it does not remove (the
+                 triple's own entity is never removed)
+    include_true False: the lists hold negatives only and 1 is added to both ``ge`` columns, so that the counts mean what
+                 rank_all's mean (the true entity ties with itself) and metrics_from_counts applies unchanged
+    Returns counts (Q, 4) int32 {gt, ge, gt_filtered, ge_filtered}; with return_scores also the candidates' scores in the
+    caller's layout ((Q, C), or (nnz,); NaN at padding and skipped entries), score_fn's values bit for bit.
+    A HIP table at a width blp_rank_lists takes goes through it (a float16 / bfloat16 table is read as it is; only the Q fixed
+    and true rows are widened); CPU tensors and other widths take the dense route: score_fn on gathered rows."""
+    model = _module(model)
+    if side not in ("head", "tail", "both"):
+        raise ValueError(f"side must be 'head', 'tail' or 'both', got {side!r}")
+    if candidates_are not in ("rows", "ids"):
+        raise ValueError(f"candidates_are must be 'rows' or 'ids', got {candidates_are!r}")
+    device = table.device
+    N, D = table.shape
+    triples = triples.to(device=device, dtype=torch.long).reshape(-1, 3)
+    ent2idx = ent2idx.to(device=device, dtype=torch.long)
+    T = triples.shape[0]
+    h, t, r = triples[:, 0], triples[:, 1], triples[:, 2]
+    heads, tails = side in ("head", "both"), side in ("tail", "both")
+    q_head = T if heads else 0
+    fixed_ids = torch.cat([x for x, on in ((t, heads), (h, tails)) if on])
+    true_ids = torch.cat([x for x, on in ((h, heads), (t, tails)) if on])
+    rel_ids = torch.cat([r] * (int(heads) + int(tails)))
+    Q = fixed_ids.shape[0]
+
+    def to_rows(ids):
+        known = (ids >= 0) & (ids < ent2idx.shape[0])
+        return torch.where(known, ent2idx[torch.where(known, ids, torch.zeros_like(ids))], torch.full_like(ids, -1))
+
+    fixed_rows, true_rows = to_rows(fixed_ids), to_rows(true_ids)
+    rel_w = model.rel_emb.weight.detach()
+    if Q and bool(((fixed_rows < 0) | (fixed_rows >= N) | (true_rows < 0) | (true_rows >= N) | (rel_ids < 0) |
+                   (rel_ids >= rel_w.shape[0])).any()):
+        raise ValueError("rank_candidates: a query's fixed or true entity has no table row, or its relation is out of range")
+    rect = None
+    if isinstance(candidates, (tuple, list)):
+        ptr, rows = (x.to(device=device, dtype=torch.long).reshape(-1) for x in candidates)
+        if ptr.shape[0] != Q + 1:
+            raise ValueError(f"candidates: ptr must have Q + 1 = {Q + 1} entries, got {ptr.shape[0]}")
+    else:
+        rect = candidates.to(device=device, dtype=torch.long)
+        if rect.dim() != 2 or rect.shape[0] != Q:
+            raise ValueError(f"candidates must be (Q, C) with Q = {Q}, got {tuple(rect.shape)}")
+        ptr = torch.arange(Q + 1, device=device, dtype=torch.long) * rect.shape[1]
+        rows = rect.reshape(-1)
+    if candidates_are == "ids":
+        rows = to_rows(rows)
+    filt = None
+    if filter_index is not None and Q:
+        seg = filter_index.segments(triples, ent2idx, device)
+        sel = torch.cat([x for x, on in ((torch.arange(T, device=device), heads), (torch.arange(T, 2 * T, device=device), tails)) if on])
+        filt = ops.SegmentFilter(seg.seg_lo[sel].contiguous(), seg.seg_hi[sel].contiguous(), seg.values,
+                                 seg.exclude[sel].contiguous(), seg.ent2idx, 0)
+    if table.is_cuda and ops.rank_lists_supported(model.rel_model, D, table.dtype):
+        if table.dtype != torch.float32:  # float32 query vectors: the Q fixed and the Q true rows, widened (exact)
+            source = table[torch.cat((fixed_rows, true_rows))].float()
+            src_fixed, src_true = torch.arange(Q, device=device), torch.arange(Q, 2 * Q, device=device)
+        else:
+            source, src_fixed, src_true = table, fixed_rows, true_rows
+        counts, scores = ops.rank_lists(model.rel_model, table, source, src_fixed, rel_w, rel_ids, q_head, ptr, rows,
+                                        true_row=src_true, filter=filt, want_scores=return_scores)
+    else:
+        dense_filt = None if filt is None else (filt.seg_lo, filt.seg_hi, filt.values, filt.exclude, filt.ent2idx)
+        counts, scores = _rank_lists_dense(model.score_fn, table, table[fixed_rows].float(), rel_w[rel_ids],
+                                           table[true_rows].float(), q_head, ptr, rows, 0, dense_filt, return_scores)
+    if not include_true:
+        counts[:, 1] += 1
+        counts[:, 3] += 1
+    if not return_scores:
+        return counts
+    return counts, (scores if rect is None else scores.reshape(rect.shape))
 
 
 def _module(model):

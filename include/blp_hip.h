@@ -500,6 +500,47 @@ int blp_topk_typed(int model, const void *table, int table_dtype, int64_t N, int
                    float *scores, void *workspace, size_t workspace_bytes, int device, void *stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Per-query candidate lists: RANK and SCORE a query (h, r, ?) / (?, r, t) against a list of table rows that belongs to that
+ * query -- the sampled negatives of an evaluation on a table of millions of rows, the candidates a first stage (BM25, a type
+ * index) hands over for re-ranking, or any sparse set of (query, entity) pairs.  Only the listed rows are read.
+ *
+ * Queries as in blp_rank_all_shard: Q = q_head + q_tail, head-replacing first; fixed_row / true_row index source (S, D) f32
+ * (row stride ld_src), rel_id indexes rel_emb (R, D) contiguous.  Candidates: the rows of table (N, D) in table_dtype
+ * (BLP_DTYPE_*, widened exactly), row stride ld -- GLOBAL rows [row_base, row_base + N).
+ * Lists: a CSR over the queries -- query q owns entries [list_ptr[q], list_ptr[q + 1]) of list_row (nnz) int64 GLOBAL rows;
+ * list_ptr (Q + 1) int64 is trusted to be non-decreasing with list_ptr[0] = 0 and list_ptr[Q] = nnz.  A list is a multiset:
+ * every entry counts, duplicates included.  There is no limit on a list's length; an empty list gives zero counts.
+ * An entry outside [row_base, row_base + N) -- the -1 of a padded rectangular (Q, C) list, a row of another candidate shard --
+ * is SKIPPED: it counts nowhere and its score slot is the quiet NaN 0x7fc00000, so per-shard counts add up to the
+ * unsharded ones.
+ * Outputs (either may be NULL, not both):
+ *   counts (Q, 4) int32 {gt, ge, gt_filt, ge_filt}: the entries of the list that score above / at least the true entity
+ *          (row true_row[q] of source; its key as blp_rank_all_shard computes it; IEEE comparisons, so a NaN counts nowhere,
+ *          as in blp_rank_from_scores); the _filt columns count only entries whose row the filter does not remove (without a
+ *          filter they repeat the first two).  The true row, if listed, is an entry like any other (it adds to ge).
+ *          counts needs true_row and the workspace; true_row == NULL goes with counts == NULL (scores only).
+ *   scores (nnz) f32, aligned with list_row: score_fn's value of every entry bit for bit (the torch-CPU order of
+ *          oracle/blp_oracle.c, sign of zero included).
+ *   filter (optional): a blp_filter with blp_rank_all's semantics (segments of entity ids through ent2idx and row_base;
+ *          exclude[q] is never removed) whose row_base MUST equal this call's (else BLP_ERR_BAD_ARG).
+ * Limits (blp_rank_lists_supported): TransE at any D % 4 == 0, D <= 1024; DistMult / ComplEx / SimplE at D in {64, 128, 256};
+ * nnz < 2^31; row_base + N <= 2^31; Q <= 2^30; table rows / source / rel_emb / counts 16-byte aligned (ld % 4 == 0, a
+ * 16-bit table: ld % 8 == 0, in elements; ld_src % 4 == 0).
+ * Workspace: blp_rank_lists_workspace_bytes(...) bytes, 256-B aligned, needed with counts only: 4 Q bytes rounded up to 256
+ * (the true keys) -- independent of N and nnz.
+ * Asynchronous on `stream`, no allocation; deterministic: long lists are split over workgroups whose partial counts are
+ * combined by integer adds, so nothing depends on the grid.
+ * (Added after 6.0.0 without a version change: no existing entry point changed.)
+ * -------------------------------------------------------------------------------------------- */
+int blp_rank_lists_supported(int model, int table_dtype, int D);
+size_t blp_rank_lists_workspace_bytes(int model, int table_dtype, int D, int64_t q_head, int64_t q_tail);
+int blp_rank_lists(int model, const void *table, int table_dtype, int64_t N, int D, int64_t ld, int64_t row_base,
+                   const float *source, int64_t S, int64_t ld_src, const int64_t *fixed_row, const float *rel_emb, int64_t R,
+                   const int64_t *rel_id, const int64_t *true_row, int64_t q_head, int64_t q_tail, const int64_t *list_ptr,
+                   const int64_t *list_row, int64_t nnz, const blp_filter *filter, int32_t *counts, float *scores,
+                   void *workspace, size_t workspace_bytes, int device, void *stream);
+
+/* --------------------------------------------------------------------------------------------
  * Re-ranking a first-stage retrieval run (reference retrieval.py rerank: BM25F candidates of DBpedia-Entity v2 re-scored
  * with entity embeddings, the mixing weight alpha chosen per fold by nDCG@100).  Candidates are a CSR over Q queries:
  * query q owns candidates [cand_ptr[q], cand_ptr[q + 1]) (cand_ptr (Q + 1) int64, cand_ptr[0] = 0, cand_ptr[Q] = C).
