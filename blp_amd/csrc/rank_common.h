@@ -80,6 +80,56 @@ hipError_t launch_filter_finalize(int model, int D, const float* table, int64_t 
                                   const FilterSpec& filter, const unsigned long long* acc, int32_t* counts,
                                   hipStream_t stream, int n_partials = 1);
 
+// Candidate sets shared between queries (rank_sets.hip; include/blp_hip.h: blp_rank_sets): set g = entries [set_ptr[g],
+// set_ptr[g + 1]) of set_row, GLOBAL rows strictly ascending; within each side the queries are grouped by set -- set g serves
+// head queries [qptr_head[g], qptr_head[g + 1]) and tail queries q_head + [qptr_tail[g], qptr_tail[g + 1]).
+struct SetLookup {
+    static constexpr bool on = true;
+    const int64_t* set_ptr;
+    const int64_t* set_row;
+    const int64_t* qptr_head;
+    const int64_t* qptr_tail;
+    int64_t G;
+    int64_t row_base;
+    // entries [lo, hi) of set_row: the set of query q (q_head: where the tail-replacing queries start)
+    __device__ __forceinline__ void set_of(int64_t q, int64_t q_head, int64_t& lo, int64_t& hi) const {
+        const int64_t* ptr = q < q_head ? qptr_head : qptr_tail;
+        const int64_t j = q < q_head ? q : q - q_head;
+        int64_t a = 0, b = G;  // ptr[a] <= j < ptr[b]: the last set whose run starts at or before j
+        while (b - a > 1) {
+            const int64_t mid = (a + b) >> 1;
+            if (ptr[mid] <= j) a = mid; else b = mid;
+        }
+        lo = set_ptr[a];
+        hi = set_ptr[a + 1];
+    }
+    __device__ __forceinline__ bool contains(int64_t lo, int64_t hi, int64_t global_row) const {
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            const int64_t v = set_row[mid];
+            if (v == global_row) return true;
+            if (v < global_row) lo = mid + 1; else hi = mid;
+        }
+        return false;
+    }
+};
+struct NoSets { static constexpr bool on = false; };  // filter_finalize_kernel without the membership test
+
+// launch_filter_finalize (one partial per query) with one more condition: a filter entry is re-scored and subtracted only if
+// its row is in the query's set.  filter.on() must hold.
+hipError_t launch_filter_finalize_sets(int model, int D, const float* table, int64_t N, int64_t ld, const QRows q_fixed,
+                                       const QRows q_rel, const float* key_true, int64_t q_head, int64_t q_tail,
+                                       const FilterSpec& filter, const SetLookup& sets, const unsigned long long* acc, int32_t* counts,
+                                       hipStream_t stream);
+
+// rank_sets.hip: counts of queries against candidate sets shared between them (include/blp_hip.h: blp_rank_sets); the
+// workspace holds the true keys, the accumulators, the coefficient rows and the G + 1 values of the unit prefix
+bool rank_sets_supported(int model, int D);
+size_t rank_sets_workspace_bytes(int D, int64_t q_head, int64_t q_tail, int64_t G);
+hipError_t launch_rank_sets(int model, int D, const float* table, int64_t N, int64_t ld, const QRows q_fixed, const QRows q_rel,
+                            const QRows q_true, int64_t q_head, int64_t q_tail, const SetLookup& sets, int64_t nnz,
+                            const FilterSpec& filter, int32_t* counts, void* workspace, int n_cu, hipStream_t stream);
+
 // ---- the bounded worst case of the pre-pass paths (round 5) --------------------------------------------------------------
 // A pre-pass pays off while it leaves little to the exact path.  When a device-side counter says it has not -- the pair lists
 // ran (nearly) full: exact ties with the true entity on whole percents of the table -- the refinement kernels stand down and

@@ -19,16 +19,13 @@ constexpr int kSlabFloats = kTileRows * kLdsStride;
 // 1. every global load of the tile up front (D/4 x 1 KiB in flight per wave), landing in e[] in the coalesced layout:
 //    e[32s + 4i .. +3] = row (row0 + 8i + lane/8), cols 32s + 4(lane%8) .. +3.  Rows past the table end are clamped to
 //    the last row (the caller masks their counts).
-template <int D, bool NT>
-__device__ __forceinline__ void tile_fetch(float (&e)[D], const float* __restrict__ table, int64_t N, int64_t ld,
-                                           int64_t row0, int lane) {
-    const int sub_row = lane >> 3;        // 8 rows per wave instruction
-    const int sub_col = (lane & 7) * 4;   // 8 x 16 B = one 128-B line per row
+//    src_of(ic<i>): where step i of the lane reads from -- row (8 i + lane / 8) of the tile, at column 4 (lane % 8) -- so a tile
+//    need not be consecutive rows (rank_sets.hip gathers the rows of a candidate set).
+template <int D, bool NT, class Src>
+__device__ __forceinline__ void tile_fetch_from(float (&e)[D], Src src_of) {
     static_for<8>([&](auto ii) {
         constexpr int i = decltype(ii)::value;
-        int64_t row = row0 + 8 * i + sub_row;
-        row = row < N ? row : N - 1;
-        const float* src = table + row * ld + sub_col;
+        const float* src = src_of(ii);
         static_for<D / kSubCols>([&](auto ss) {
             constexpr int s = decltype(ss)::value;
             typedef float floatx4 __attribute__((ext_vector_type(4)));
@@ -37,6 +34,19 @@ __device__ __forceinline__ void tile_fetch(float (&e)[D], const float* __restric
             e[32 * s + 4 * i] = v.x; e[32 * s + 4 * i + 1] = v.y;
             e[32 * s + 4 * i + 2] = v.z; e[32 * s + 4 * i + 3] = v.w;
         });
+    });
+}
+
+template <int D, bool NT>
+__device__ __forceinline__ void tile_fetch(float (&e)[D], const float* __restrict__ table, int64_t N, int64_t ld,
+                                           int64_t row0, int lane) {
+    const int sub_row = lane >> 3;        // 8 rows per wave instruction
+    const int sub_col = (lane & 7) * 4;   // 8 x 16 B = one 128-B line per row
+    tile_fetch_from<D, NT>(e, [&](auto ii) {
+        constexpr int i = decltype(ii)::value;
+        int64_t row = row0 + 8 * i + sub_row;
+        row = row < N ? row : N - 1;
+        return table + row * ld + sub_col;
     });
 }
 

@@ -766,8 +766,239 @@ def rank_candidates(model, table, triples, candidates, ent2idx, *, side="both", 
     return counts, (scores if rect is None else scores.reshape(rect.shape))
 
 
+# ----------------------------------------------------------------------------------- candidate sets shared between queries
+def _sets_from_pairs(owner, rows, num_sets):
+    """(ptr (G + 1,), rows (nnz,)) of the sets {rows[i] : owner[i] == g}: each set sorted ascending, duplicates dropped."""
+    span = int(rows.max()) + 1 if rows.numel() else 1
+    keys = torch.unique(owner * span + rows)  # sorted: by set, then by row
+    counts = torch.bincount(torch.div(keys, span, rounding_mode="floor"), minlength=num_sets)
+    ptr = torch.zeros(num_sets + 1, dtype=torch.long, device=rows.device)
+    ptr[1:] = torch.cumsum(counts, 0)
+    return ptr, keys % span
+
+
+class CandidateSets:
+    """G candidate sets of table rows that queries share (rank_in_sets), held as a CSR: ``ptr`` (G + 1,) and ``rows`` (nnz,)
+    int64, the rows of a set ascending and without duplicates -- a set is a set.  Built from
+      * a sequence of G sets, each a Python list or a 1-D tensor of rows, in any order, duplicates allowed;
+      * a padded rectangle: a (G, C) tensor, negative entries are padding;
+      * a CSR: CandidateSets(ptr=..., rows=...) (sorted and de-duplicated per set like the others).
+    Sorted, de-duplicated and validated once, here: a negative row (outside a rectangle's padding), a row >= ``num_rows`` (if
+    given) or a ptr that is not a non-decreasing run from 0 to len(rows) raises ValueError."""
+
+    def __init__(self, sets=None, *, ptr=None, rows=None, num_rows=None, device=None):
+        if (sets is None) == (ptr is None) or (ptr is None) != (rows is None):
+            raise ValueError("CandidateSets: give either the sets (a sequence of sets or a padded (G, C) tensor) or ptr and rows")
+        if sets is not None and isinstance(sets, torch.Tensor):
+            if sets.dim() != 2 or sets.dtype.is_floating_point or sets.dtype is torch.bool:
+                raise ValueError("CandidateSets: a tensor must be a padded (G, C) rectangle of integer rows")
+            rect = sets.to(torch.long)
+            G = rect.shape[0]
+            owner = torch.arange(G, device=rect.device).unsqueeze(1).expand_as(rect)[rect >= 0]
+            flat = rect[rect >= 0]
+        elif sets is not None:
+            parts = [torch.as_tensor(s, dtype=torch.long).reshape(-1) for s in sets]
+            G = len(parts)
+            dev0 = parts[0].device if parts else torch.device("cpu")
+            flat = torch.cat(parts) if parts else torch.empty(0, dtype=torch.long)
+            owner = torch.repeat_interleave(torch.arange(G, device=dev0), torch.tensor([p.numel() for p in parts], dtype=torch.long, device=dev0)) \
+                if parts else flat
+        else:
+            ptr = torch.as_tensor(ptr).reshape(-1)
+            flat = torch.as_tensor(rows).reshape(-1)
+            if ptr.dtype.is_floating_point or flat.dtype.is_floating_point:
+                raise ValueError("CandidateSets: ptr and rows must be integer tensors")
+            ptr, flat = ptr.to(torch.long), flat.to(device=ptr.device, dtype=torch.long)
+            G = ptr.shape[0] - 1
+            if G < 0 or int(ptr[0]) != 0 or int(ptr[-1]) != flat.shape[0] or bool((ptr[1:] < ptr[:-1]).any()):
+                raise ValueError("CandidateSets: ptr must run from 0 to len(rows) without decreasing")
+            owner = torch.repeat_interleave(torch.arange(G, device=ptr.device), ptr[1:] - ptr[:-1], output_size=flat.shape[0])
+        if flat.numel() and int(flat.min()) < 0:
+            raise ValueError("CandidateSets: negative row")
+        if num_rows is not None and flat.numel() and int(flat.max()) >= int(num_rows):
+            raise ValueError(f"CandidateSets: row {int(flat.max())} outside the table of {int(num_rows)} rows")
+        self.ptr, self.rows = _sets_from_pairs(owner, flat, G)
+        if device is not None:
+            self.ptr, self.rows = self.ptr.to(device), self.rows.to(device)
+
+    @property
+    def num_sets(self):
+        return self.ptr.shape[0] - 1
+
+    def to(self, device):
+        return _SetsView(self.ptr.to(device), self.rows.to(device))
+
+    def tolist(self):
+        p, r = self.ptr.tolist(), self.rows.tolist()
+        return [r[p[g]:p[g + 1]] for g in range(len(p) - 1)]
+
+    def contains(self, set_ids, rows):
+        """(n,) bool: is rows[i] in set set_ids[i]?  (searchsorted over the CSR, whose (set, row) keys ascend)"""
+        if not self.rows.numel():
+            return torch.zeros(rows.shape, dtype=torch.bool, device=rows.device)
+        span = max(int(self.rows.max()), int(rows.max()) if rows.numel() else 0) + 1
+        owner = torch.repeat_interleave(torch.arange(self.num_sets, device=self.rows.device), self.ptr[1:] - self.ptr[:-1],
+                                        output_size=self.rows.shape[0])
+        keys, want = owner * span + self.rows, set_ids * span + rows
+        pos = torch.searchsorted(keys, want).clamp(max=keys.shape[0] - 1)
+        return (keys[pos] == want) & (rows >= 0)
+
+
+class _SetsView(CandidateSets):
+    """A CandidateSets over tensors that are already a valid CSR (no second normalisation)."""
+
+    def __init__(self, ptr, rows):
+        self.ptr, self.rows = ptr, rows
+
+
+def relation_candidate_sets(graph_triples, num_relations, ent2idx):
+    """The candidate sets of type-constrained evaluation, 2 R of them: set r = the table rows of the entities seen as HEAD of
+    relation r in ``graph_triples`` ((T, 3): head, tail, rel) -- the relation's domain --, set R + r = those seen as its TAIL
+    (its range).  Ids without a row in ``ent2idx`` are dropped.  Torch ops only: CPU or device, wherever the triples are."""
+    R = int(num_relations)
+    triples = graph_triples.to(torch.long).reshape(-1, 3)
+    ent2idx = ent2idx.to(device=triples.device, dtype=torch.long)
+    ids = torch.cat((triples[:, 0], triples[:, 1]))
+    owner = torch.cat((triples[:, 2], triples[:, 2] + R))
+    if owner.numel() and (int(triples[:, 2].min()) < 0 or int(triples[:, 2].max()) >= R):
+        raise ValueError(f"relation_candidate_sets: a relation outside [0, {R})")
+    known = (ids >= 0) & (ids < ent2idx.shape[0])
+    rows = torch.where(known, ent2idx[torch.where(known, ids, torch.zeros_like(ids))], torch.full_like(ids, -1))
+    return _SetsView(*_sets_from_pairs(owner[rows >= 0], rows[rows >= 0], 2 * R))
+
+
+def _rank_sets_dense(score_fn, table, fixed, rel, true_vec, q_head, set_ptr, set_rows, qptr_head, qptr_tail, row_base, filt,
+                     max_bytes=1 << 28):
+    """The dense route of rank_in_sets: score_fn of each set's gathered rows against its group's queries, in (row slab, query
+    chunk) pieces of bounded bytes, the comparisons against the true score, the filter through _filtered_pairs (an entry counts
+    only if its row is in the set).  Queries grouped by set within each side, as blp_rank_sets takes them; fixed / rel /
+    true_vec (Q, D) float32.  CPU tensors, widths and table dtypes blp_rank_sets does not take; on CPU tensors it is the oracle
+    of the fused route.  Returns counts (Q, 4) int32."""
+    Q, (N, D) = fixed.shape[0], table.shape
+    dev = table.device
+    acc = torch.zeros((Q, 4), dtype=torch.int64, device=dev)
+    true = torch.cat((score_fn(true_vec[:q_head], fixed[:q_head], rel[:q_head]), score_fn(fixed[q_head:], true_vec[q_head:], rel[q_head:])))
+    budget = max(1, max_bytes // (12 * D))  # (row, query) pairs per piece: three (pairs, D) float32 operands
+    sp, qh, qt = set_ptr.tolist(), qptr_head.tolist(), qptr_tail.tolist()
+    for g in range(len(sp) - 1):
+        local = set_rows[sp[g]:sp[g + 1]] - row_base
+        local = local[(local >= 0) & (local < N)]
+        runs = [(head, a, b) for head, a, b in ((True, qh[g], qh[g + 1]), (False, q_head + qt[g], q_head + qt[g + 1])) if a < b]
+        if not local.numel() or not runs:
+            continue
+        for r0 in range(0, local.shape[0], budget):
+            rows = local[r0:r0 + budget]
+            n = rows.shape[0]
+            e = table[rows].float()
+            step = max(1, budget // n)
+            for head, a, b in runs:
+                for lo in range(a, b, step):
+                    hi = min(lo + step, b)
+                    c = hi - lo
+                    ee = e.unsqueeze(0).expand(c, n, D).reshape(c * n, D)
+                    ff = fixed[lo:hi].unsqueeze(1).expand(c, n, D).reshape(c * n, D)
+                    rr = rel[lo:hi].unsqueeze(1).expand(c, n, D).reshape(c * n, D)
+                    s = (score_fn(ee, ff, rr) if head else score_fn(ff, ee, rr)).reshape(c, n)
+                    kt = true[lo:hi].unsqueeze(1)
+                    gt, ge = s > kt, s >= kt
+                    keep = torch.ones_like(gt)
+                    f_owner, f_local = _filtered_pairs(filt, lo, hi, row_base, N, dev)
+                    if f_owner.numel():
+                        pos = torch.searchsorted(rows, f_local).clamp(max=n - 1)
+                        hit = rows[pos] == f_local
+                        keep[f_owner[hit], pos[hit]] = False
+                    for col, mask in enumerate((gt, ge, gt & keep, ge & keep)):
+                        acc[lo:hi, col] += mask.sum(1)
+    return acc.to(torch.int32)
+
+
+def rank_in_sets(model, table, triples, sets, ent2idx, *, set_ids=None, side="both", filter_index=None, add_true=True):
+    """Rank every triple's true entity against a candidate SET that it shares with other queries -- type-constrained
+    evaluation (the default: a head query of relation r against set r, a tail query against set R + r of
+    relation_candidate_sets), per-type or per-language pools, one first-stage pool per group of queries.
+    triples      (T, 3) (head, tail, rel); ``side`` "head": (?, r, t); "tail": (h, r, ?); "both": Q = 2 T queries in
+                 predict_links' order [heads | tails]
+    sets         CandidateSets of table rows
+    set_ids      (Q,) the set of every query, in that order; an id outside [0, G) raises ValueError
+    ent2idx      utils.make_ent2idx map (entity id -> table row); the fixed and the true entity of a query must have a row
+    filter_index utils.FilterIndex of the known edges: the filtered columns leave out the entries of the set it removes (the
+                 triple's own entity is never removed)
+    add_true     True: a query whose true entity is not in its set gets 1 added to both ``ge`` columns -- the true entity always
+                 competes and ties with itself, so metrics_from_counts applies unchanged; False: the counts over the set as it is
+    Returns counts (Q, 4) int32 {gt, ge, gt_filtered, ge_filtered} in the caller's order.
+    A float32 HIP table at 64 / 128 / 256 goes through blp_rank_sets (every row of a set is fetched once per chunk of 128
+    queries of its group); CPU tensors, other widths and 16-bit tables take the dense route: score_fn on gathered rows."""
+    model = _module(model)
+    if side not in ("head", "tail", "both"):
+        raise ValueError(f"side must be 'head', 'tail' or 'both', got {side!r}")
+    device = table.device
+    N, D = table.shape
+    triples = triples.to(device=device, dtype=torch.long).reshape(-1, 3)
+    ent2idx = ent2idx.to(device=device, dtype=torch.long)
+    T = triples.shape[0]
+    h, t, r = triples[:, 0], triples[:, 1], triples[:, 2]
+    heads, tails = side in ("head", "both"), side in ("tail", "both")
+    q_head = T if heads else 0
+    fixed_ids = torch.cat([x for x, on in ((t, heads), (h, tails)) if on])
+    true_ids = torch.cat([x for x, on in ((h, heads), (t, tails)) if on])
+    rel_ids = torch.cat([r] * (int(heads) + int(tails)))
+    Q = fixed_ids.shape[0]
+
+    def to_rows(ids):
+        known = (ids >= 0) & (ids < ent2idx.shape[0])
+        return torch.where(known, ent2idx[torch.where(known, ids, torch.zeros_like(ids))], torch.full_like(ids, -1))
+
+    fixed_rows, true_rows = to_rows(fixed_ids), to_rows(true_ids)
+    rel_w = model.rel_emb.weight.detach()
+    R = rel_w.shape[0]
+    if Q and bool(((fixed_rows < 0) | (fixed_rows >= N) | (true_rows < 0) | (true_rows >= N) | (rel_ids < 0) | (rel_ids >= R)).any()):
+        raise ValueError("rank_in_sets: a query's fixed or true entity has no table row, or its relation is out of range")
+    set_ptr, set_rows = sets.ptr.to(device), sets.rows.to(device)
+    G = set_ptr.shape[0] - 1
+    if set_rows.numel() and int(set_rows.max()) >= N:
+        raise ValueError(f"rank_in_sets: the sets name row {int(set_rows.max())}, the table has {N} rows")
+    if set_ids is None:
+        set_ids = torch.cat([x for x, on in ((r, heads), (r + R, tails)) if on])
+    set_ids = set_ids.to(device=device, dtype=torch.long).reshape(-1)
+    if set_ids.shape[0] != Q:
+        raise ValueError(f"set_ids needs one entry per query ({Q}), got {set_ids.shape[0]}")
+    if Q and (int(set_ids.min()) < 0 or int(set_ids.max()) >= G):
+        raise ValueError(f"rank_in_sets: a set id outside [0, {G})")
+    # the queries of each side grouped by set (stable: a group keeps the caller's order)
+    order_h = torch.sort(set_ids[:q_head], stable=True).indices
+    order_t = torch.sort(set_ids[q_head:], stable=True).indices + q_head
+    perm = torch.cat((order_h, order_t))
+    qptr_head = torch.zeros(G + 1, dtype=torch.long, device=device)
+    qptr_tail = torch.zeros(G + 1, dtype=torch.long, device=device)
+    qptr_head[1:] = torch.cumsum(torch.bincount(set_ids[:q_head], minlength=G), 0)
+    qptr_tail[1:] = torch.cumsum(torch.bincount(set_ids[q_head:], minlength=G), 0)
+    g_fixed, g_true, g_rel = fixed_rows[perm], true_rows[perm], rel_ids[perm]
+    filt = None
+    if filter_index is not None and Q:
+        seg = filter_index.segments(triples, ent2idx, device)
+        sel = torch.cat([x for x, on in ((torch.arange(T, device=device), heads), (torch.arange(T, 2 * T, device=device), tails)) if on])[perm]
+        filt = ops.SegmentFilter(seg.seg_lo[sel].contiguous(), seg.seg_hi[sel].contiguous(), seg.values,
+                                 seg.exclude[sel].contiguous(), seg.ent2idx, 0)
+    if Q == 0:
+        return torch.empty((0, 4), dtype=torch.int32, device=device)
+    if table.is_cuda and table.dtype == torch.float32 and ops.rank_sets_supported(model.rel_model, D):
+        grouped = ops.rank_sets(model.rel_model, table, table, g_fixed, rel_w, g_rel, q_head, g_true, set_ptr, set_rows, qptr_head,
+                                qptr_tail, filter=filt)
+    else:
+        dense_filt = None if filt is None else (filt.seg_lo, filt.seg_hi, filt.values, filt.exclude, filt.ent2idx)
+        grouped = _rank_sets_dense(model.score_fn, table, table[g_fixed].float(), rel_w[g_rel], table[g_true].float(), q_head,
+                                   set_ptr, set_rows, qptr_head, qptr_tail, 0, dense_filt)
+    counts = torch.empty_like(grouped)
+    counts[perm] = grouped
+    if add_true:
+        absent = ~_SetsView(set_ptr, set_rows).contains(set_ids, true_rows)
+        counts[:, 1] += absent.to(torch.int32)
+        counts[:, 3] += absent.to(torch.int32)
+    return counts
+
+
 def _module(model):
-    wrappers = (torch.nn.DataParallel, torch.nn.parallel.DistributedDataParallel)
+    wrappers =(torch.nn.DataParallel, torch.nn.parallel.DistributedDataParallel)
     return model.module if isinstance(model, wrappers) else model
 
 

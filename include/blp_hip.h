@@ -541,6 +541,46 @@ int blp_rank_lists(int model, const void *table, int table_dtype, int64_t N, int
                    void *workspace, size_t workspace_bytes, int device, void *stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Candidate sets SHARED between queries: rank a query against the rows of a set that a whole group of queries ranks against --
+ * type-constrained evaluation (a head query of relation r against the entities seen as heads of r, a tail query against
+ * those seen as its tails), per-relation / per-type / per-language pools, one first-stage pool for a group of queries.
+ * A row of a set is fetched once per (set, chunk of 128 queries of its group), not once per query as a per-query list of
+ * blp_rank_lists would be.
+ *
+ * Table: (N, D) f32, row stride ld -- GLOBAL rows [row_base, row_base + N).  Queries as in blp_rank_all_shard: Q = q_head +
+ * q_tail, head-replacing first; fixed_row / true_row index source (S, D) f32 (row stride ld_src), rel_id indexes rel_emb
+ * (R, D) contiguous.
+ * Sets: a CSR over G sets -- set g owns entries [set_ptr[g], set_ptr[g + 1]) of set_row (nnz) int64 GLOBAL rows, STRICTLY
+ * ASCENDING within a set (a set is a set; the filter's membership test is a binary search); set_ptr (G + 1) int64 is trusted
+ * to be non-decreasing with set_ptr[0] = 0 and set_ptr[G] = nnz.  An entry outside [row_base, row_base + N) is SKIPPED, so
+ * per-shard counts add up to the unsharded ones.
+ * Which set a query ranks against: within each side the queries are ordered by non-decreasing set.  Set g serves the
+ * head-replacing queries [qset_ptr_head[g], qset_ptr_head[g + 1]) and the tail-replacing queries q_head + [qset_ptr_tail[g],
+ * qset_ptr_tail[g + 1]) -- both (G + 1) int64, non-decreasing, qset_ptr_head from 0 to q_head, qset_ptr_tail (counted from
+ * q_head) from 0 to q_tail.  A set may serve both sides, one side or no query; a query of an empty set gets zero counts.
+ * counts (Q, 4) int32 {gt, ge, gt_filt, ge_filt}, overwritten, in the caller's (grouped) query order: blp_rank_all's counts
+ *   taken over the entries of the query's set only -- the true entity's key as blp_rank_all_shard computes it, every entry
+ *   by the exact f32 kernel's arithmetic (the reference's counts bit for bit).  The true entity adds to ge if and only if
+ *   its row is in the set.
+ * filter (optional): a blp_filter with blp_rank_all's semantics whose row_base MUST equal this call's (else
+ *   BLP_ERR_BAD_ARG).  An entry removes its row from the _filt columns only if that row is in the query's set.
+ * Limits (blp_rank_sets_supported): the four models at D in {64, 128, 256}; Q <= 2^30; nnz < 2^31; row_base + N <= 2^31;
+ * table / source / rel_emb / counts 16-byte aligned, ld % 4 == 0, ld_src % 4 == 0.
+ * Workspace: blp_rank_sets_workspace_bytes(model, D, q_head, q_tail, G) bytes, 256-B aligned: true keys, accumulators,
+ * coefficient rows (2 D floats per query) and G + 1 int64 of work-unit offsets -- independent of N and nnz.
+ * Asynchronous on `stream`, no host synchronisation, no allocation; nothing about set or group sizes is read on the host.
+ * Deterministic: partial counts are combined by integer adds, so nothing depends on the grid.
+ * (Added after 6.0.0 without a version change: no existing entry point changed.)
+ * -------------------------------------------------------------------------------------------- */
+int blp_rank_sets_supported(int model, int D);
+size_t blp_rank_sets_workspace_bytes(int model, int D, int64_t q_head, int64_t q_tail, int64_t G);
+int blp_rank_sets(int model, const float *table, int64_t N, int D, int64_t ld, int64_t row_base, const float *source, int64_t S,
+                  int64_t ld_src, const int64_t *fixed_row, const float *rel_emb, int64_t R, const int64_t *rel_id,
+                  const int64_t *true_row, int64_t q_head, int64_t q_tail, const int64_t *set_ptr, const int64_t *set_row,
+                  int64_t nnz, int64_t G, const int64_t *qset_ptr_head, const int64_t *qset_ptr_tail, const blp_filter *filter,
+                  int32_t *counts, void *workspace, size_t workspace_bytes, int device, void *stream);
+
+/* --------------------------------------------------------------------------------------------
  * Re-ranking a first-stage retrieval run (reference retrieval.py rerank: BM25F candidates of DBpedia-Entity v2 re-scored
  * with entity embeddings, the mixing weight alpha chosen per fold by nDCG@100).  Candidates are a CSR over Q queries:
  * query q owns candidates [cand_ptr[q], cand_ptr[q + 1]) (cand_ptr (Q + 1) int64, cand_ptr[0] = 0, cand_ptr[Q] = C).

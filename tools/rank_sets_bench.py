@@ -1,0 +1,160 @@
+"""Time blp_rank_sets (counts against candidate sets shared by groups of queries, filtered) next to the route the library
+offered for the same job before it: blp_rank_lists on the sets expanded into one list per query.
+
+For each workload: the same queries, sets and filter; the expansion is done once, outside the timing (the lists of the expanded
+route are cut into calls of < 2^30 entries, blp_rank_lists' limit being 2^31 - 1); the counts of the two routes must be equal
+before anything is timed.  The two routes alternate step by step in one process, each bracketed by device events; warm-up,
+then --steps steps; one JSON line with the median and p90 of both, their ratio and the achieved gather bandwidth of the new
+call (rows fetched: one per set entry and chunk of 128 queries of its group, D x 4 bytes each).
+
+    python tools/rank_sets_bench.py [--steps 30] [--warmup 3] [--only NAME ...] [--out FILE.jsonl]
+
+  fb15k237-{transe,distmult}   105 740 queries, 14 541 x 128 table, 474 sets of 50 .. 8 000 rows (log-uniform)
+  longtable-transe             13 788 queries, 4.6 M x 128 table, 1 644 sets of 10^3 .. 10^6 rows (log-uniform)
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from blp_amd import ops  # noqa: E402
+
+WORKLOADS = {
+    "fb15k237-transe": dict(model="transe", N=14_541, D=128, Q=105_740, G=474, set_min=50, set_max=8000),
+    "fb15k237-distmult": dict(model="distmult", N=14_541, D=128, Q=105_740, G=474, set_min=50, set_max=8000),
+    "longtable-transe": dict(model="transe", N=4_600_000, D=128, Q=13_788, G=1644, set_min=1000, set_max=1_000_000),
+}
+FILTER_PER_QUERY = 8  # entries of a query's filter segment, half of them members of its set
+MAX_LIST_ENTRIES = 1 << 30
+QUERY_CHUNK = 128
+
+
+def measure(calls, steps, warmup):
+    ev = {n: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for n in calls}
+    out = {n: [] for n in calls}
+    for i in range(warmup + steps):
+        for n, fn in calls.items():
+            ev[n][0].record()
+            fn()
+            ev[n][1].record()
+        torch.cuda.synchronize()
+        if i >= warmup:
+            for n in calls:
+                out[n].append(ev[n][0].elapsed_time(ev[n][1]))
+    return out
+
+
+def stats(ms):
+    a = np.asarray(ms)
+    return {"median": round(float(np.median(a)), 4), "p90": round(float(np.percentile(a, 90)), 4)}
+
+
+def run(name, cfg, steps, warmup):
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev).manual_seed(0)
+    rng = np.random.default_rng(0)
+    N, D, Q, G = cfg["N"], cfg["D"], cfg["Q"], cfg["G"]
+    table = torch.randn((N, D), generator=g, device=dev)
+    table = torch.nn.functional.normalize(table, dim=-1) if cfg["model"] == "transe" else table * 0.1
+    R = 237
+    rel_w = (torch.rand((R, D), generator=g, device=dev) - 0.5) * 0.25
+    sizes = np.exp(rng.uniform(np.log(cfg["set_min"]), np.log(cfg["set_max"]), G)).astype(np.int64)
+    set_ptr = torch.zeros(G + 1, dtype=torch.long, device=dev)
+    set_ptr[1:] = torch.cumsum(torch.from_numpy(sizes).to(dev), 0)
+    set_row = torch.cat([torch.randperm(N, generator=g, device=dev)[:int(n)].sort().values for n in sizes])
+    q_head = Q // 2
+    ids = torch.cat((torch.randint(0, G, (q_head,), generator=g, device=dev).sort().values,
+                     torch.randint(0, G, (Q - q_head,), generator=g, device=dev).sort().values))
+    qh = torch.zeros(G + 1, dtype=torch.long, device=dev)
+    qt = torch.zeros(G + 1, dtype=torch.long, device=dev)
+    qh[1:] = torch.cumsum(torch.bincount(ids[:q_head], minlength=G), 0)
+    qt[1:] = torch.cumsum(torch.bincount(ids[q_head:], minlength=G), 0)
+    fixed = torch.randint(0, N, (Q,), generator=g, device=dev)
+    true = torch.randint(0, N, (Q,), generator=g, device=dev)
+    rel_ids = torch.randint(0, R, (Q,), generator=g, device=dev)
+    n_per = (set_ptr[1:] - set_ptr[:-1])[ids]
+    first = set_ptr[ids]
+    # a value occurs once per filter segment (blp_filter's contract): consecutive members of the set, distinct other rows, and
+    # -1 (removes nothing) where one of those is a listed member already
+    half = FILTER_PER_QUERY // 2
+    k = torch.arange(half, device=dev).unsqueeze(0)
+    inside = set_row[first.unsqueeze(1) + (torch.randint(0, 1 << 30, (Q, 1), generator=g, device=dev) + k) % n_per.unsqueeze(1)]
+    other = (torch.randint(0, N, (Q, 1), generator=g, device=dev) + k * 3571) % N
+    other = torch.where((other.unsqueeze(2) == inside.unsqueeze(1)).any(2), torch.full_like(other, -1), other)
+    seg = torch.cat((inside, other), 1)
+    lo = torch.arange(Q, device=dev) * FILTER_PER_QUERY
+    filt = ops.SegmentFilter(lo, lo + FILTER_PER_QUERY, seg.reshape(-1).contiguous(), None, None, 0)
+    counts = torch.empty((Q, 4), dtype=torch.int32, device=dev)
+
+    def fused():
+        ops.rank_sets(cfg["model"], table, table, fixed, rel_w, rel_ids, q_head, true, set_ptr, set_row, qh, qt, filter=filt, out=counts)
+
+    # the expanded route: per-query lists, in calls of at most MAX_LIST_ENTRIES entries, each of one side
+    list_ptr_all = torch.zeros(Q + 1, dtype=torch.long, device=dev)
+    list_ptr_all[1:] = torch.cumsum(n_per, 0)
+    host_ptr = list_ptr_all.tolist()
+    calls, a = [], 0
+    while a < Q:
+        end = q_head if a < q_head else Q
+        b = a + 1
+        while b < end and host_ptr[b + 1] - host_ptr[a] <= MAX_LIST_ENTRIES:
+            b += 1
+        n = host_ptr[b] - host_ptr[a]
+        owner = torch.repeat_interleave(torch.arange(a, b, device=dev), n_per[a:b], output_size=n)
+        rows = set_row[first[owner] + torch.arange(host_ptr[a], host_ptr[b], device=dev) - list_ptr_all[owner]]
+        del owner
+        part = ops.SegmentFilter(filt.seg_lo[a:b].contiguous(), filt.seg_hi[a:b].contiguous(), filt.values, None, None, 0)
+        calls.append((a, b, (list_ptr_all[a:b + 1] - host_ptr[a]).contiguous(), rows, part))
+        a = b
+    expanded_counts = torch.empty((Q, 4), dtype=torch.int32, device=dev)
+
+    def expanded():
+        for a, b, ptr, rows, part in calls:
+            ops.rank_lists(cfg["model"], table, table, fixed[a:b], rel_w, rel_ids[a:b], min(max(q_head - a, 0), b - a), ptr, rows,
+                           true_row=true[a:b], filter=part, out=(expanded_counts[a:b], None))
+
+    fused()
+    expanded()
+    same = bool(torch.equal(counts, expanded_counts))
+    if not same:
+        return {"workload": name, **cfg, "counts_equal": False}
+    ms = measure({"sets": fused, "expanded_lists": expanded}, steps, warmup)
+    s, e = stats(ms["sets"]), stats(ms["expanded_lists"])
+    chunks = (torch.div(qh[1:] - qh[:-1] + QUERY_CHUNK - 1, QUERY_CHUNK, rounding_mode="floor") +
+              torch.div(qt[1:] - qt[:-1] + QUERY_CHUNK - 1, QUERY_CHUNK, rounding_mode="floor"))
+    fetched = int(((set_ptr[1:] - set_ptr[:-1]) * chunks).sum()) * D * 4
+    pairs = int(n_per.sum())
+    return {"workload": name, **cfg, "set_entries": int(set_row.numel()), "pairs": pairs, "expanded_calls": len(calls),
+            "expanded_index_bytes": pairs * 8, "filter_entries_per_query": FILTER_PER_QUERY, "counts_equal": same, "sets_ms": s,
+            "expanded_lists_ms": e, "expanded_over_sets": round(e["median"] / s["median"], 2), "fetched_bytes": fetched,
+            "gather_TBps": round(fetched / (s["median"] * 1e-3) / 1e12, 3),
+            "pairs_per_s": round(pairs / (s["median"] * 1e-3), 0), "steps": steps}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--only", nargs="*")
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    for name, cfg in WORKLOADS.items():
+        if args.only and name not in args.only:
+            continue
+        line = json.dumps(run(name, cfg, args.steps, args.warmup))
+        print(line, flush=True)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "a") as fh:
+                fh.write(line + "\n")
+        ops.release_workspaces()
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
