@@ -832,13 +832,15 @@ size_t blp_rank_sets_workspace_bytes(int model, int D, int64_t q_head, int64_t q
     return blp::rank_sets_workspace_bytes(D, q_head, q_tail, G);
 }
 
-int blp_rank_sets(int model, const float* table, int64_t N, int D, int64_t ld, int64_t row_base, const float* source, int64_t S,
-                  int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R, const int64_t* rel_id,
-                  const int64_t* true_row, int64_t q_head, int64_t q_tail, const int64_t* set_ptr, const int64_t* set_row, int64_t nnz,
-                  int64_t G, const int64_t* qset_ptr_head, const int64_t* qset_ptr_tail, const blp_filter* filter, int32_t* counts,
-                  void* workspace, size_t workspace_bytes, int device, void* stream) {
-    const char* who = "blp_rank_sets";
+// blp_rank_sets and blp_rank_sets_typed: the argument checks (messages under the entry's name `who`), then the launch
+static int rank_sets_call(const char* who, int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld,
+                          int64_t row_base, const float* source, int64_t S, int64_t ld_src, const int64_t* fixed_row,
+                          const float* rel_emb, int64_t R, const int64_t* rel_id, const int64_t* true_row, int64_t q_head,
+                          int64_t q_tail, const int64_t* set_ptr, const int64_t* set_row, int64_t nnz, int64_t G,
+                          const int64_t* qset_ptr_head, const int64_t* qset_ptr_tail, const blp_filter* filter, int32_t* counts,
+                          void* workspace, size_t workspace_bytes, int device, void* stream) {
     if (!valid_model(model)) return fail(BLP_ERR_BAD_ARG, "%s: unknown model %d", who, model);
+    if (!valid_table_dtype(table_dtype)) return fail(BLP_ERR_BAD_ARG, "%s: unknown table dtype %d", who, table_dtype);
     if (!blp_rank_sets_supported(model, D))
         return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (64 / 128 / 256: see blp_rank_sets_supported)", who, D);
     if (N < 0 || q_head < 0 || q_tail < 0 || ld < D || row_base < 0 || nnz < 0 || G < 0)
@@ -854,8 +856,12 @@ int blp_rank_sets(int model, const float* table, int64_t N, int D, int64_t ld, i
         return fail(BLP_ERR_BAD_ARG, "%s: %lld queries but no set, or NULL set_ptr / qset_ptr_head / qset_ptr_tail", who, (long long)Q);
     if (nnz > 0 && !set_row) return fail(BLP_ERR_BAD_ARG, "%s: %lld set entries but NULL set_row", who, (long long)nnz);
     if (N > 0 && !table) return fail(BLP_ERR_BAD_ARG, "%s: NULL table", who);
-    if (!aligned16(table) || (ld & 3) || !aligned16(source) || (ld_src & 3) || ld_src < D || !aligned16(rel_emb) || !aligned16(counts))
-        return fail(BLP_ERR_BAD_ARG, "%s: table / source / rel_emb / counts must be 16-byte aligned, ld %% 4 == 0, ld_src %% 4 == 0, ld_src >= D",
+    if (!table_rows_aligned(table, table_dtype, ld) || !aligned16(source) || (ld_src & 3) || ld_src < D || !aligned16(rel_emb) ||
+        !aligned16(counts))
+        return fail(BLP_ERR_BAD_ARG, table_dtype == BLP_DTYPE_F32
+                                         ? "%s: table / source / rel_emb / counts must be 16-byte aligned, ld %% 4 == 0, ld_src %% 4 == 0, ld_src >= D"
+                                         : "%s: table / source / rel_emb / counts must be 16-byte aligned, ld %% 8 == 0 (a 16-bit table's row "
+                                           "stride, in elements), ld_src %% 4 == 0, ld_src >= D",
                     who);
     blp::FilterSpec spec;
     if (filter) {
@@ -877,11 +883,40 @@ int blp_rank_sets(int model, const float* table, int64_t N, int D, int64_t ld, i
     int cu = 0;
     if (int rc = compute_units(device, &cu)) return rc;
     const blp::SetLookup sets{set_ptr, set_row, qset_ptr_head, qset_ptr_tail, G, row_base};
-    hipError_t err = blp::launch_rank_sets(model, D, table, N, ld, blp::QRows::rows_of(source, fixed_row, ld_src),
+    hipError_t err = blp::launch_rank_sets(model, D, table_dtype, table, N, ld, blp::QRows::rows_of(source, fixed_row, ld_src),
                                            blp::QRows::rows_of(rel_emb, rel_id, D), blp::QRows::rows_of(source, true_row, ld_src), q_head,
                                            q_tail, sets, nnz, spec, counts, workspace, cu, static_cast<hipStream_t>(stream));
-    if (err != hipSuccess) return hip_fail(err, "blp_rank_sets launch");
+    if (err != hipSuccess) return hip_fail(err, table_dtype == BLP_DTYPE_F32 ? "blp_rank_sets launch" : "blp_rank_sets_typed launch");
     return BLP_OK;
+}
+
+int blp_rank_sets(int model, const float* table, int64_t N, int D, int64_t ld, int64_t row_base, const float* source, int64_t S,
+                  int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R, const int64_t* rel_id,
+                  const int64_t* true_row, int64_t q_head, int64_t q_tail, const int64_t* set_ptr, const int64_t* set_row, int64_t nnz,
+                  int64_t G, const int64_t* qset_ptr_head, const int64_t* qset_ptr_tail, const blp_filter* filter, int32_t* counts,
+                  void* workspace, size_t workspace_bytes, int device, void* stream) {
+    return rank_sets_call("blp_rank_sets", model, table, BLP_DTYPE_F32, N, D, ld, row_base, source, S, ld_src, fixed_row, rel_emb, R,
+                          rel_id, true_row, q_head, q_tail, set_ptr, set_row, nnz, G, qset_ptr_head, qset_ptr_tail, filter, counts,
+                          workspace, workspace_bytes, device, stream);
+}
+
+int blp_rank_sets_typed_supported(int model, int table_dtype, int D) {
+    return valid_model(model) && blp::rank_sets_typed_supported(model, table_dtype, D) ? 1 : 0;
+}
+
+size_t blp_rank_sets_typed_workspace_bytes(int model, int table_dtype, int D, int64_t q_head, int64_t q_tail, int64_t G) {
+    if (!blp_rank_sets_typed_supported(model, table_dtype, D) || q_head < 0 || q_tail < 0 || G < 0) return 0;
+    return blp::rank_sets_workspace_bytes(D, q_head, q_tail, G);
+}
+
+int blp_rank_sets_typed(int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld, int64_t row_base,
+                        const float* source, int64_t S, int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R,
+                        const int64_t* rel_id, const int64_t* true_row, int64_t q_head, int64_t q_tail, const int64_t* set_ptr,
+                        const int64_t* set_row, int64_t nnz, int64_t G, const int64_t* qset_ptr_head, const int64_t* qset_ptr_tail,
+                        const blp_filter* filter, int32_t* counts, void* workspace, size_t workspace_bytes, int device, void* stream) {
+    return rank_sets_call(table_dtype == BLP_DTYPE_F32 ? "blp_rank_sets" : "blp_rank_sets_typed", model, table, table_dtype, N, D, ld,
+                          row_base, source, S, ld_src, fixed_row, rel_emb, R, rel_id, true_row, q_head, q_tail, set_ptr, set_row, nnz, G,
+                          qset_ptr_head, qset_ptr_tail, filter, counts, workspace, workspace_bytes, device, stream);
 }
 
 // ---- re-ranking a retrieval run (rerank.hip)

@@ -122,12 +122,14 @@ hipError_t launch_filter_finalize_sets(int model, int D, const float* table, int
                                        const FilterSpec& filter, const SetLookup& sets, const unsigned long long* acc, int32_t* counts,
                                        hipStream_t stream);
 
-// rank_sets.hip: counts of queries against candidate sets shared between them (include/blp_hip.h: blp_rank_sets); the
-// workspace holds the true keys, the accumulators, the coefficient rows and the G + 1 values of the unit prefix
+// rank_sets.hip: counts of queries against candidate sets shared between them (include/blp_hip.h: blp_rank_sets,
+// blp_rank_sets_typed); the table f32 or 16-bit (dtype: table_elem.h; ld in elements); the workspace -- the same for every
+// dtype -- holds the true keys, the accumulators, the coefficient rows and the G + 1 values of the unit prefix
 bool rank_sets_supported(int model, int D);
+bool rank_sets_typed_supported(int model, int dtype, int D);
 size_t rank_sets_workspace_bytes(int D, int64_t q_head, int64_t q_tail, int64_t G);
-hipError_t launch_rank_sets(int model, int D, const float* table, int64_t N, int64_t ld, const QRows q_fixed, const QRows q_rel,
-                            const QRows q_true, int64_t q_head, int64_t q_tail, const SetLookup& sets, int64_t nnz,
+hipError_t launch_rank_sets(int model, int D, int dtype, const void* table, int64_t N, int64_t ld, const QRows q_fixed,
+                            const QRows q_rel, const QRows q_true, int64_t q_head, int64_t q_tail, const SetLookup& sets, int64_t nnz,
                             const FilterSpec& filter, int32_t* counts, void* workspace, int n_cu, hipStream_t stream);
 
 // ---- the bounded worst case of the pre-pass paths (round 5) --------------------------------------------------------------

@@ -181,6 +181,7 @@ struct RowsF32 {  // load_tile: every load of the tile, then the transpose
 
 // A 16-bit table (T = _Float16 / __bf16, row stride ld elements, rows 16-byte aligned): w[s][i] = this lane's 16 bytes of
 // piece s (columns 64 s ..) of row 8 i + lane / 8 -- 8 rows x 128 B per instruction, as rank_stream16.hip loads them.
+// (tile16.h holds the same body with the row source taken out, for rank_sets_kernel.h: a fix here belongs there too.)
 template <int D, class T>
 struct Rows16 {
     static constexpr int NP = D / 64;

@@ -493,10 +493,12 @@ def rank_lists(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, li
     return counts, scores
 
 
-def rank_sets_supported(rel_model, dim):
-    """True if rank_sets takes this width (include/blp_hip.h: blp_rank_sets_supported -- the four models at 64 / 128 / 256; the
-    table is float32)."""
-    return bool(_lib.lib().blp_rank_sets_supported(_lib.MODEL_IDS[rel_model], int(dim)))
+def rank_sets_supported(rel_model, dim, dtype=torch.float32):
+    """True if rank_sets takes this width and table dtype (include/blp_hip.h: blp_rank_sets_typed_supported -- the four models at
+    64 / 128 / 256; a float32, float16 or bfloat16 table)."""
+    if dtype not in TABLE_DTYPES:
+        return False
+    return bool(_lib.lib().blp_rank_sets_typed_supported(_lib.MODEL_IDS[rel_model], TABLE_DTYPES[dtype], int(dim)))
 
 
 def rank_sets_workspace_bytes(rel_model, D, q_head, q_tail, num_sets):
@@ -505,19 +507,22 @@ def rank_sets_workspace_bytes(rel_model, D, q_head, q_tail, num_sets):
 
 def rank_sets(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, true_row, set_ptr, set_row, qset_ptr_head,
               qset_ptr_tail, filter=None, row_base=0, out=None):
-    """Counts of queries against candidate sets that queries SHARE (blp_rank_sets).  Queries as in rank_all_shard -- head-replacing
+    """Counts of queries against candidate sets that queries SHARE (blp_rank_sets, blp_rank_sets_typed).  Queries as in rank_all_shard -- head-replacing
     [0, q_head), then tail-replacing; fixed_row / true_row (Q,) index ``source`` (S, D) float32, rel_ids (Q,) index ``rel_emb``
     (R, D) -- and, within each side, GROUPED by set: set g serves head queries [qset_ptr_head[g], qset_ptr_head[g + 1]) and
     tail queries q_head + [qset_ptr_tail[g], qset_ptr_tail[g + 1]) (both (G + 1,), from 0 to q_head / to Q - q_head).
-    Set g is entries [set_ptr[g], set_ptr[g + 1]) of ``set_row`` (nnz,): GLOBAL rows of ``table`` (N, D) float32 -- which holds
+    Set g is entries [set_ptr[g], set_ptr[g + 1]) of ``set_row`` (nnz,): GLOBAL rows of ``table`` (N, D) (float32 / float16 /
+    bfloat16; a 16-bit table needs a float32 ``source``: the counts are those of the table widened to float32) -- which holds
     global rows [row_base, row_base + N) --, strictly ascending within a set; entries outside the shard are skipped.
     Returns counts (Q, 4) int32 {gt, ge, gt_filtered, ge_filtered} over the entries of each query's set (``filter``: a
     SegmentFilter whose row_base is ``row_base``; an entry of it counts only if its row is in the set)."""
     _require_device(table, source, fixed_row, rel_emb, rel_ids, true_row, set_ptr, set_row, qset_ptr_head, qset_ptr_tail)
-    if table.dtype != torch.float32:
-        raise TypeError(f"rank_sets reads a float32 table, got {table.dtype}")
+    if table.dtype not in TABLE_DTYPES:
+        raise TypeError(f"rank_sets reads a float32, float16 or bfloat16 table, got {table.dtype}")
+    if source is table and table.dtype != torch.float32:
+        raise TypeError("a 16-bit table needs a float32 `source` for the queries' vectors")
     same = source is table
-    table = _f32_rows(table, "table")
+    table = _table_rows(table, "table")
     source = table if same else _f32_rows(source, "source")
     rel_emb = _f32_rows(rel_emb, "rel_emb").contiguous()
     N, D = table.shape
@@ -533,7 +538,7 @@ def rank_sets(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, tru
         raise ValueError("set_ptr, qset_ptr_head and qset_ptr_tail need G + 1 entries each")
     if not 0 <= q_head <= Q:
         raise ValueError(f"q_head = {q_head} outside [0, {Q}]")
-    if not rank_sets_supported(rel_model, D):
+    if not rank_sets_supported(rel_model, D, table.dtype):
         raise ValueError(f"rank_sets: D = {D} not supported (64 / 128 / 256: see rank_sets_supported)")
     if filter is not None and int(filter.row_base) != int(row_base):
         raise ValueError(f"rank_sets: the filter's row_base {filter.row_base} differs from row_base {row_base}")
@@ -546,16 +551,18 @@ def rank_sets(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, tru
     L = _lib.lib()
     model = _lib.MODEL_IDS[rel_model]
     stream = torch._C._cuda_getCurrentRawStream(dev.index)
-    ws_bytes = L.blp_rank_sets_workspace_bytes(model, D, q_head, Q - q_head, G)
+    tdt = TABLE_DTYPES[table.dtype]
+    ws_bytes = L.blp_rank_sets_typed_workspace_bytes(model, tdt, D, q_head, Q - q_head, G)
     workspace = _workspace(dev, stream, ws_bytes)
     spec = None if filter is None else _filter_spec(filter, Q, dev)
-    status = L.blp_rank_sets(model, table.data_ptr(), N, D, table.stride(0) if N > 1 else D, int(row_base), source.data_ptr(),
-                             source.shape[0], source.stride(0) if source.shape[0] > 1 else D, fixed_row.data_ptr(), rel_emb.data_ptr(),
-                             rel_emb.shape[0], rel_ids.data_ptr(), true_row.data_ptr(), q_head, Q - q_head, set_ptr.data_ptr(),
-                             _addr(set_row) if nnz else None, nnz, G, qset_ptr_head.data_ptr(), qset_ptr_tail.data_ptr(), spec,
-                             counts.data_ptr(), workspace.data_ptr(), ws_bytes, dev.index, stream)
+    status = L.blp_rank_sets_typed(model, table.data_ptr(), tdt, N, D, table.stride(0) if tdt or N > 1 else D, int(row_base),
+                                   source.data_ptr(), source.shape[0], source.stride(0) if source.shape[0] > 1 else D,
+                                   fixed_row.data_ptr(), rel_emb.data_ptr(), rel_emb.shape[0], rel_ids.data_ptr(), true_row.data_ptr(),
+                                   q_head, Q - q_head, set_ptr.data_ptr(), _addr(set_row) if nnz else None, nnz, G,
+                                   qset_ptr_head.data_ptr(), qset_ptr_tail.data_ptr(), spec, counts.data_ptr(), workspace.data_ptr(),
+                                   ws_bytes, dev.index, stream)
     if status:
-        _lib.check(status, "blp_rank_sets")
+        _lib.check(status, "blp_rank_sets_typed" if tdt else "blp_rank_sets")
     return counts
 
 

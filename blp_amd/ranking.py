@@ -872,7 +872,7 @@ def _rank_sets_dense(score_fn, table, fixed, rel, true_vec, q_head, set_ptr, set
     """The dense route of rank_in_sets: score_fn of each set's gathered rows against its group's queries, in (row slab, query
     chunk) pieces of bounded bytes, the comparisons against the true score, the filter through _filtered_pairs (an entry counts
     only if its row is in the set).  Queries grouped by set within each side, as blp_rank_sets takes them; fixed / rel /
-    true_vec (Q, D) float32.  CPU tensors, widths and table dtypes blp_rank_sets does not take; on CPU tensors it is the oracle
+    true_vec (Q, D) float32.  CPU tensors and the widths and table dtypes blp_rank_sets_typed does not take; on CPU tensors it is the oracle
     of the fused route.  Returns counts (Q, 4) int32."""
     Q, (N, D) = fixed.shape[0], table.shape
     dev = table.device
@@ -926,8 +926,9 @@ def rank_in_sets(model, table, triples, sets, ent2idx, *, set_ids=None, side="bo
     add_true     True: a query whose true entity is not in its set gets 1 added to both ``ge`` columns -- the true entity always
                  competes and ties with itself, so metrics_from_counts applies unchanged; False: the counts over the set as it is
     Returns counts (Q, 4) int32 {gt, ge, gt_filtered, ge_filtered} in the caller's order.
-    A float32 HIP table at 64 / 128 / 256 goes through blp_rank_sets (every row of a set is fetched once per chunk of 128
-    queries of its group); CPU tensors, other widths and 16-bit tables take the dense route: score_fn on gathered rows."""
+    A float32, float16 or bfloat16 HIP table at 64 / 128 / 256 goes through blp_rank_sets / blp_rank_sets_typed (every row of a
+    set is fetched once per chunk of 128 queries of its group; a 16-bit table is read as it is, only the Q fixed and the Q true
+    rows are gathered and widened); CPU tensors and other widths take the dense route: score_fn on gathered rows."""
     model = _module(model)
     if side not in ("head", "tail", "both"):
         raise ValueError(f"side must be 'head', 'tail' or 'both', got {side!r}")
@@ -981,8 +982,16 @@ def rank_in_sets(model, table, triples, sets, ent2idx, *, set_ids=None, side="bo
                                  seg.exclude[sel].contiguous(), seg.ent2idx, 0)
     if Q == 0:
         return torch.empty((0, 4), dtype=torch.int32, device=device)
-    if table.is_cuda and table.dtype == torch.float32 and ops.rank_sets_supported(model.rel_model, D):
-        grouped = ops.rank_sets(model.rel_model, table, table, g_fixed, rel_w, g_rel, q_head, g_true, set_ptr, set_rows, qptr_head,
+    if table.is_cuda and ops.rank_sets_supported(model.rel_model, D, table.dtype):
+        if table.dtype != torch.float32:
+            # float32 query vectors: the Q fixed rows, then the Q true rows, gathered and widened (exact) by the library's own
+            # kernel (blp_gather_triple_vectors: 64-bit offsets, a table of more than 2^31 bytes included)
+            pairs = torch.stack((g_fixed, g_true, torch.zeros_like(g_fixed)), dim=1)
+            source = ops.gather_triple_vectors(pairs, None, table)
+            src_fixed, src_true = torch.arange(Q, device=device), torch.arange(Q, 2 * Q, device=device)
+        else:
+            source, src_fixed, src_true = table, g_fixed, g_true
+        grouped = ops.rank_sets(model.rel_model, table, source, src_fixed, rel_w, g_rel, q_head, src_true, set_ptr, set_rows, qptr_head,
                                 qptr_tail, filter=filt)
     else:
         dense_filt = None if filt is None else (filt.seg_lo, filt.seg_hi, filt.values, filt.exclude, filt.ent2idx)

@@ -7,7 +7,11 @@ before anything is timed.  The two routes alternate step by step in one process,
 then --steps steps; one JSON line with the median and p90 of both, their ratio and the achieved gather bandwidth of the new
 call (rows fetched: one per set entry and chunk of 128 queries of its group, D x 4 bytes each).
 
-    python tools/rank_sets_bench.py [--steps 30] [--warmup 3] [--only NAME ...] [--out FILE.jsonl]
+    python tools/rank_sets_bench.py [--steps 30] [--warmup 3] [--only NAME ...] [--out FILE.jsonl] [--table16 {f16,bf16}]
+
+--table16: the table rounded to IEEE half / bfloat16 instead; blp_rank_sets_typed on the 16-bit table alternates with
+blp_rank_sets on that table widened to f32 (the yardstick), counts required equal first; one JSON line with both medians,
+their ratio (16-bit over f32) and the gather bandwidth of the 16-bit call (D x 2 bytes per fetched row).
 
   fb15k237-{transe,distmult}   105 740 queries, 14 541 x 128 table, 474 sets of 50 .. 8 000 rows (log-uniform)
   longtable-transe             13 788 queries, 4.6 M x 128 table, 1 644 sets of 10^3 .. 10^6 rows (log-uniform)
@@ -54,7 +58,7 @@ def stats(ms):
     return {"median": round(float(np.median(a)), 4), "p90": round(float(np.percentile(a, 90)), 4)}
 
 
-def run(name, cfg, steps, warmup):
+def run(name, cfg, steps, warmup, table16=None):
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(0)
     rng = np.random.default_rng(0)
@@ -90,6 +94,10 @@ def run(name, cfg, steps, warmup):
     lo = torch.arange(Q, device=dev) * FILTER_PER_QUERY
     filt = ops.SegmentFilter(lo, lo + FILTER_PER_QUERY, seg.reshape(-1).contiguous(), None, None, 0)
     counts = torch.empty((Q, 4), dtype=torch.int32, device=dev)
+    if table16:  # (the f32 original is not kept: the 16-bit copy and its widened image replace it)
+        small = table.to({"f16": torch.float16, "bf16": torch.bfloat16}[table16])
+        del table
+        return run16(name, cfg, steps, warmup, table16, small, rel_w, fixed, true, rel_ids, q_head, set_ptr, set_row, qh, qt, filt, counts)
 
     def fused():
         ops.rank_sets(cfg["model"], table, table, fixed, rel_w, rel_ids, q_head, true, set_ptr, set_row, qh, qt, filter=filt, out=counts)
@@ -136,17 +144,50 @@ def run(name, cfg, steps, warmup):
             "pairs_per_s": round(pairs / (s["median"] * 1e-3), 0), "steps": steps}
 
 
+def run16(name, cfg, steps, warmup, table16, small, rel_w, fixed, true, rel_ids, q_head, set_ptr, set_row, qh, qt, filt, counts):
+    """blp_rank_sets_typed on the 16-bit table next to blp_rank_sets on that table widened to f32."""
+    D, Q = cfg["D"], cfg["Q"]
+    wide = small.float()
+    counts16 = torch.empty_like(counts)
+    # the queries' f32 vectors: the Q fixed rows, then the Q true rows, widened (blp_gather_triple_vectors, as
+    # ranking.rank_in_sets gathers them) -- the same source for both calls
+    source = ops.gather_triple_vectors(torch.stack((fixed, true, torch.zeros_like(fixed)), dim=1), None, small)
+    src_fixed, src_true = torch.arange(Q, device=wide.device), torch.arange(Q, 2 * Q, device=wide.device)
+
+    def f32():
+        ops.rank_sets(cfg["model"], wide, source, src_fixed, rel_w, rel_ids, q_head, src_true, set_ptr, set_row, qh, qt, filter=filt, out=counts)
+
+    def t16():
+        ops.rank_sets(cfg["model"], small, source, src_fixed, rel_w, rel_ids, q_head, src_true, set_ptr, set_row, qh, qt, filter=filt, out=counts16)
+
+    f32()
+    t16()
+    same = bool(torch.equal(counts, counts16))
+    if not same:
+        return {"workload": name, **cfg, "table16": table16, "counts_equal": False}
+    ms = measure({"f32": f32, "table16": t16}, steps, warmup)
+    a, b = stats(ms["f32"]), stats(ms["table16"])
+    chunks = (torch.div(qh[1:] - qh[:-1] + QUERY_CHUNK - 1, QUERY_CHUNK, rounding_mode="floor") +
+              torch.div(qt[1:] - qt[:-1] + QUERY_CHUNK - 1, QUERY_CHUNK, rounding_mode="floor"))
+    fetched_rows = int(((set_ptr[1:] - set_ptr[:-1]) * chunks).sum())
+    return {"workload": name, **cfg, "table16": table16, "set_entries": int(set_row.numel()), "filter_entries_per_query": FILTER_PER_QUERY,
+            "counts_equal": same, "f32_ms": a, "table16_ms": b, "table16_over_f32": round(b["median"] / a["median"], 3),
+            "fetched_bytes_table16": fetched_rows * D * 2, "gather_TBps_table16": round(fetched_rows * D * 2 / (b["median"] * 1e-3) / 1e12, 3),
+            "gather_TBps_f32": round(fetched_rows * D * 4 / (a["median"] * 1e-3) / 1e12, 3), "steps": steps}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--only", nargs="*")
     ap.add_argument("--out")
+    ap.add_argument("--table16", choices=("f16", "bf16"))
     args = ap.parse_args()
     for name, cfg in WORKLOADS.items():
         if args.only and name not in args.only:
             continue
-        line = json.dumps(run(name, cfg, args.steps, args.warmup))
+        line = json.dumps(run(name, cfg, args.steps, args.warmup, args.table16))
         print(line, flush=True)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
