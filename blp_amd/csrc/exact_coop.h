@@ -94,6 +94,40 @@ __device__ __forceinline__ float transe_key_64(const TE* pe, const float* pf, co
     return -sum;
 }
 
+// The same key by ONE lane from its own three rows, 16 columns (twelve 16-byte loads) at a time: no slab, no shuffles, a
+// dozen registers besides the loads in flight -- for a caller that has neither to spare and whose CU has other work to
+// hide the latency behind (the pre-pass kernel's own refinement, rank_sad.hip).  A load instruction of the wave touches up
+// to 64 lines, but a lane's four loads of a row are one 64-byte half-line, so the lines are fetched from L2 once.
+// Operation for operation what transe_key_64 computes, so the same bits.
+template <int D>
+__device__ __forceinline__ float transe_key_lane(const float* pe, const float* pf, const float* pr, bool head) {
+    const float* pa = head ? pe : pf;  // (a + r) - b: head-replacing (e + r) - f, tail-replacing (f + r) - e
+    const float* pb = head ? pf : pe;
+    float sum = 0.0f;
+#pragma unroll 1
+    for (int c = 0; c < D; c += 16) {
+        float4 a[4], r[4], b[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i] = *reinterpret_cast<const float4*>(pa + c + 4 * i);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r[i] = *reinterpret_cast<const float4*>(pr + c + 4 * i);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) b[i] = *reinterpret_cast<const float4*>(pb + c + 4 * i);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float av[4] = {a[i].x, a[i].y, a[i].z, a[i].w}, rv[4] = {r[i].x, r[i].y, r[i].z, r[i].w},
+                        bv[4] = {b[i].x, b[i].y, b[i].z, b[i].w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float x = av[k] + rv[k];
+                x = x - bv[k];
+                sum = sum + fabsf(x);
+            }
+        }
+    }
+    return -sum;
+}
+
 // The same at a run-time width D (D % 4 == 0; the bag-of-words / DKRL widths 300, 768), straight from the entity and
 // relation vectors: head-replacing query (e + r) - f with f = the tail, tail-replacing (f + r) - e with f = the head
 // (models.py:222-223).  The last chunk of a width that is not a multiple of 32 loads only the columns that exist.

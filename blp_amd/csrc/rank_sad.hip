@@ -24,11 +24,16 @@
 //           Undecided pairs are ~0.2 % for FB15k-237-like data.  A workgroup lists up to kSQuota pairs;
 //           beyond that the (query, 64-candidate tile) segment contributes nothing and its bit is set in
 //           a flag bitmap.
-//   pass 2  listed pairs and flagged segments are re-scored with the order-exact Scorer<TRANSE> (the
-//           code that produced s_true) and counted exactly.
+//   pass 2  listed pairs and flagged segments are re-scored with the order-exact arithmetic of Scorer<TRANSE> (the
+//           code that produced s_true) and counted exactly.  A workgroup whose list is short (<= kSInlineCap pairs:
+//           practically all of them on embedding-like data, ~75 pairs on average) does that itself before it exits --
+//           the gathers are all latency, which the CU's other workgroups cover with their SADs -- and writes nothing to
+//           the global list; longer lists are compacted into the global list for sad_refine_pairs_kernel, whose launch
+//           otherwise finds the list empty.  Flagged segments go to sad_refine_tiles_kernel.
 // Non-finite values anywhere, or a degenerate range, make every kernel of the pre-pass a no-op and the
 // segment refinement sweep all tiles: the result is exact in every case, just slower.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -215,6 +220,20 @@ struct SadTiles {
 #endif
 constexpr unsigned kSadChunkBlock = BLP_SAD_CHUNK_BLOCK;  // query chunks whose workgroups run together on an XCD
 
+// Undecided pairs up to which a pre-pass workgroup refines its own list (rank_sad_kernel's epilogue).  ms per step, FB15k-237
+// block | clustered table | 5 % ties (profiles/sad_inline_refine/cap_scan.log: one box, one or two 100-step samples per value,
+// round-to-round spread ~0.01; the parent 3.169 | 3.384 | 15.75): 0: 3.169 | - | -, 64: 3.159 | 3.377 | 15.74, 128: 3.055,
+// 256: 3.057 | 3.138 | 15.71, 512: 3.059, 1024: 3.062 | 3.135 | (*).  What the data settle are the bounds: 64 is too small (the
+// average list holds ~75 pairs), and nothing is gained beyond 256 on either table; among 128 .. 512 they do not choose.
+// (*) measured while the gate still counted the global list's cursor alone: lists refined here did not move it, the 5 %-ties
+// block never tripped the gate and took 131 ms.  The gate now counts every listed pair (SadParams::n_listed) and trips where
+// it always did, whatever the cap; 1024 was not measured again.
+#ifndef BLP_SAD_INLINE_CAP
+#define BLP_SAD_INLINE_CAP 256
+#endif
+constexpr unsigned kSInlineCap = BLP_SAD_INLINE_CAP;
+static_assert(kSInlineCap <= kSQuota, "the pooled list is the four slices of pair_s");
+
 // -DBLP_TIMING: per wave of the kernel below, shader-clock ticks and ticks of the constant 100 MHz counter, summed: their
 // ratio is the clock the kernel ran at (tools/gemm_ab.py --sad)
 #ifdef BLP_TIMING
@@ -232,7 +251,9 @@ __global__ __launch_bounds__(kSW * 64, (TPW * D / 2 <= 64 ? 5 : TPW * D / 2 <= 1
     const uint4* __restrict__ cimg, const unsigned* __restrict__ resid, int64_t n_rows, int n_groups, int q_per_group,
     const unsigned* __restrict__ qimg, const int2* __restrict__ thr, int64_t Q, int words_per_query,
     unsigned long long* __restrict__ acc,
-    unsigned* __restrict__ flags, uint2* __restrict__ pairs, SadParams* __restrict__ params) {
+    unsigned* __restrict__ flags, uint2* __restrict__ pairs, SadParams* __restrict__ params,
+    const float* __restrict__ table, int64_t ld, const QRows q_fixed, const QRows q_rel, int64_t q_head,
+    const float* __restrict__ key_true) {
     if (!sad_scale(params).ok) return;
 #ifdef BLP_TIMING
     const unsigned long long clk0 = __builtin_readcyclecounter(), wall0 = __builtin_amdgcn_s_memrealtime();
@@ -376,15 +397,43 @@ __global__ __launch_bounds__(kSW * 64, (TPW * D / 2 <= 64 ? 5 : TPW * D / 2 <= 1
     }
     if (lane == 0) wave_used[wave] = my_pairs;
     __syncthreads();
-    if (tid == 0) {
-        unsigned total = 0;
-        for (int w = 0; w < kSW; ++w) { wave_base[w] = total; total += wave_used[w]; }
-        const unsigned base = total ? atomicAdd(&params->n_pairs, total) : 0u;
-        for (int w = 0; w < kSW; ++w) wave_base[w] += base;
+    unsigned start[kSW + 1];  // the four slices pooled: slice w holds entries [start[w], start[w + 1]) (workgroup-uniform)
+    start[0] = 0;
+#pragma unroll
+    for (int w = 0; w < kSW; ++w) start[w + 1] = start[w] + __builtin_amdgcn_readfirstlane(wave_used[w]);
+    const unsigned total = start[kSW];
+    // every listed pair counts for the gate (and for sad_prepass_stats), wherever it is refined: the gate trips where it did
+    // when all lists went through the global one
+    if (tid == 0 && total) atomicAdd(&params->n_listed, total);
+    if (total <= kSInlineCap) {
+        // A short list is refined here, by wave 0, 64 pooled pairs per trip, instead of going through the global list and a
+        // launch of its own: the trip is all latency (three gathered 512-byte rows per pair, ~2 % of the pre-pass's VALU
+        // work), and the CU's other workgroups keep the SAD pipe busy meanwhile.  Same keys as sad_refine_pairs_kernel,
+        // bit for bit; rows are slab-relative, like the list's.  Nothing is written to the list, no space reserved in it.
+        // (When the gate says heavy, fallback_prep zeroes acc after this kernel: what is added here is recounted.)
+        if (wave == 0) {
+            for (unsigned base = 0; base < total; base += 64) {
+                const bool live = base + lane < total;
+                const unsigned t = live ? base + lane : base;  // idle lanes of the last trip: the first pair's rows again
+                const unsigned w = (unsigned)(t >= start[1]) + (unsigned)(t >= start[2]) + (unsigned)(t >= start[3]);
+                const unsigned first = w == 0 ? start[0] : w == 1 ? start[1] : w == 2 ? start[2] : start[3];
+                const uint2 p = pair_s[w * (kSQuota / kSW) + (t - first)];
+                const int64_t q = p.x;
+                const float key = transe_key_lane<D>(table + (int64_t)p.y * ld, q_fixed.row(q), q_rel.row(q), q < q_head);
+                const float kt = key_true[q];
+                const unsigned long long gt = live && key > kt, ge_ = live && key >= kt;
+                if (gt | ge_) atomicAdd(acc + q, gt | (ge_ << 32));
+            }
+        }
+    } else {  // a long one: compacted into the global list for sad_refine_pairs_kernel
+        if (tid == 0) {
+            const unsigned base = atomicAdd(&params->n_pairs, total);
+            for (int w = 0; w < kSW; ++w) wave_base[w] = base + start[w];
+        }
+        __syncthreads();
+        for (int w = 0; w < kSW; ++w)
+            for (unsigned i = tid; i < wave_used[w]; i += kSW * 64) pairs[wave_base[w] + i] = pair_s[w * (kSQuota / kSW) + i];
     }
-    __syncthreads();
-    for (int w = 0; w < kSW; ++w)
-        for (unsigned i = tid; i < wave_used[w]; i += kSW * 64) pairs[wave_base[w] + i] = pair_s[w * (kSQuota / kSW) + i];
 #ifdef BLP_TIMING
     if (lane == 0) {
         atomicAdd(&g_sad_timing[0], __builtin_readcyclecounter() - clk0);
@@ -597,8 +646,12 @@ hipError_t sad_prepass_stats(int D, int64_t N, int64_t q_head, int64_t q_tail, c
     unsigned long long host[3] = {0, 0, 0};
     const hipError_t err = launch_count_bits(w.flags, (q_head + q_tail) * words, w.pairs, &w.params->n_pairs, false, host, stream);
     out->flagged_rows = (long long)host[0] * 64;  // a flag = one (query, 64-candidate tile)
-    out->listed = (long long)host[2];             // one entry per undecided pair
-    return err;
+    if (err != hipSuccess) return err;
+    unsigned n_listed = 0;  // (host[2] is the global list's cursor: the long lists only)
+    hipError_t err2 = hipMemcpyAsync(&n_listed, &w.params->n_listed, 4, hipMemcpyDeviceToHost, stream);
+    if (err2 == hipSuccess) err2 = hipStreamSynchronize(stream);
+    out->listed = (long long)n_listed;  // one per undecided pair, wherever it was refined
+    return err2;
 }
 
 size_t rank_sad_workspace_bytes(int model, int D, int64_t N, int64_t q_head, int64_t q_tail) {
@@ -654,18 +707,19 @@ static hipError_t rank_sad_impl(const float* table, int64_t N, int64_t ld, const
         if (slab0 > 0) {
             err = hipMemsetAsync(w.flags, 0, (size_t)Q * words * 4, stream);
             if (err != hipSuccess) return err;
-            err = hipMemsetAsync(&w.params->n_pairs, 0, 4, stream);
+            static_assert(offsetof(SadParams, n_listed) == offsetof(SadParams, n_pairs) + 4, "one memset clears both counters");
+            err = hipMemsetAsync(&w.params->n_pairs, 0, 8, stream);
             if (err != hipSuccess) return err;
         }
         const float* slab = table + slab0 * ld;
         rank_sad_kernel<D, TPW><<<dim3((unsigned)n_blocks), kSW * 64, 0, stream>>>(
             w.cimg + (slab0 / 64) * (D / 8) * 64, w.resid + slab0, n_rows, (int)n_groups, per_group, w.qimg, w.thr, Q, words, w.acc,
-            w.flags, w.pairs, w.params);
+            w.flags, w.pairs, w.params, slab, ld, q_fixed, q_rel, q_head, w.key_true);
         const int64_t pair_blocks = (n_blocks * kSQuota + 63) / 64;  // 64 pairs per single-wave workgroup and iteration
         // heavy <=> the workgroups' lists are >= 90 % full (capacity: kSQuota entries each): exact ties on whole percents of the
         // table -- the flagged tiles would then cost 64 exact scores per flag (132 ms for the FB15k-237 block at 5 % ties) where
         // the exact kernel re-ranks everything in 8
-        const Gate gate{w.fallback_coef ? &w.params->n_pairs : nullptr, (unsigned)((n_blocks * kSQuota / 10 * 9) < 0xffffffffll ? n_blocks * kSQuota / 10 * 9 : 0xffffffffll)};
+        const Gate gate{w.fallback_coef ? &w.params->n_listed : nullptr, (unsigned)((n_blocks * kSQuota / 10 * 9) < 0xffffffffll ? n_blocks * kSQuota / 10 * 9 : 0xffffffffll)};
         sad_refine_pairs_kernel<D><<<dim3((unsigned)(pair_blocks < (int64_t)n_cu * 40 ? pair_blocks : (int64_t)n_cu * 40)), 64, 0, stream>>>(
             slab, ld, q_fixed, q_rel, w.key_true, q_head, w.pairs, w.params, w.acc, gate);
         sad_refine_tiles_kernel<D><<<dim3((unsigned)((Q + kSweepQueries - 1) / kSweepQueries)), 256, 0, stream>>>(

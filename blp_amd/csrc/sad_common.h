@@ -28,10 +28,13 @@ constexpr unsigned kSRowExact = 0xFFFFFFFFu;  // resid[] of a row the pre-pass m
 // marked rows / queries take the slow path (one Inf in the FB15k-237 table: 121 ms with the old global off-switch).
 struct SadParams {
     int lo_ord, hi_ord;     // range, as order-preserving ints
-    unsigned nonfinite;     // number of non-finite values seen (information only)
-    unsigned n_pairs;       // pairs listed in the current pass
+    unsigned n_pairs;       // pairs in the global list of the current pass (the list's cursor)
+    unsigned n_listed;      // undecided pairs the workgroups of the current pass listed, in the global list or refined by the
+                            // workgroup itself (rank_sad.hip): the gate's counter and prepass_stats' figure (directly after
+                            // n_pairs: one 8-byte memset clears both)
     double sum, sumsq;      // of the finite values (partial results; the final record holds the totals)
     unsigned long long count;
+    unsigned nonfinite;     // number of non-finite values seen (information only)
 };
 constexpr int kSRangeBlocks = 1024;  // partial results of the range pass
 constexpr float kSClampSigmas = 16.0f;
@@ -125,7 +128,7 @@ __device__ __forceinline__ SadParams sad_range_finish_wave(const SadParams* __re
     }
     r.wave_reduce();
     SadParams p = r.record();
-    p.n_pairs = 0;
+    p.n_pairs = p.n_listed = 0;
     if (r.count > 0 && r.lo <= r.hi) {  // clamp the range to mean +- kSClampSigmas standard deviations
         const double mean = r.sum / (double)r.count;
         const double var = r.sumsq / (double)r.count - mean * mean;
