@@ -89,7 +89,7 @@ const char* const kKnobNames[blp::KNOB_COUNT] = {"rank_kernel", "gemm_kernel", "
                                                  "sad_min_queries", "gemm_pass_words", "gemm_tiles_per_chunk",
                                                  "exact_query_chunk", "small_kernel",
                                                  "stream_kernel", "dkrl_split", "mfma_selftest", "inbatch_probe", "inbatch_shares",
-                                                 "rank_sets_grid"};
+                                                 "rank_sets_grid", "topk_sets_grid"};
 #endif
 
 }  // namespace
@@ -917,6 +917,69 @@ int blp_rank_sets_typed(int model, const void* table, int table_dtype, int64_t N
     return rank_sets_call(table_dtype == BLP_DTYPE_F32 ? "blp_rank_sets" : "blp_rank_sets_typed", model, table, table_dtype, N, D, ld,
                           row_base, source, S, ld_src, fixed_row, rel_emb, R, rel_id, true_row, q_head, q_tail, set_ptr, set_row, nnz, G,
                           qset_ptr_head, qset_ptr_tail, filter, counts, workspace, workspace_bytes, device, stream);
+}
+
+// ---- filtered top-k inside candidate sets shared between queries (topk_sets.hip)
+int blp_topk_sets_supported(int model, int D, int k) { return valid_model(model) && blp::topk_sets_supported(model, D, k) ? 1 : 0; }
+
+size_t blp_topk_sets_workspace_bytes(int model, int D, int64_t q_head, int64_t q_tail, int64_t G, int64_t nnz, int k) {
+    if (!blp_topk_sets_supported(model, D, k) || q_head < 0 || q_tail < 0 || G < 0 || nnz < 0 || nnz >= (1ll << 31) ||
+        q_head + q_tail > (1ll << 31) / k)
+        return 0;
+    return blp::topk_sets_workspace_bytes(model, D, q_head, q_tail, G, nnz, k);
+}
+
+int blp_topk_sets(int model, const float* table, int64_t N, int D, int64_t ld, int64_t row_base, const float* source, int64_t S,
+                  int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R, const int64_t* rel_id, int64_t q_head,
+                  int64_t q_tail, int k, const int64_t* set_ptr, const int64_t* set_row, int64_t nnz, int64_t G,
+                  const int64_t* qset_ptr_head, const int64_t* qset_ptr_tail, const blp_filter* filter, int64_t* rows, float* scores,
+                  void* workspace, size_t workspace_bytes, int device, void* stream) {
+    const char* who = "blp_topk_sets";
+    if (!valid_model(model)) return fail(BLP_ERR_BAD_ARG, "%s: unknown model %d", who, model);
+    if (k < 1 || k > 256) return fail(BLP_ERR_BAD_ARG, "%s: k = %d outside [1, 256]", who, k);
+    if (!blp_topk_sets_supported(model, D, k))
+        return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (64 / 128 / 256: see blp_topk_sets_supported)", who, D);
+    if (N < 0 || q_head < 0 || q_tail < 0 || ld < D || row_base < 0 || nnz < 0 || G < 0)
+        return fail(BLP_ERR_BAD_ARG, "%s: negative size / row_base or ld < D (N=%lld q_head=%lld q_tail=%lld ld=%lld nnz=%lld G=%lld)", who,
+                    (long long)N, (long long)q_head, (long long)q_tail, (long long)ld, (long long)nnz, (long long)G);
+    if (nnz >= (1ll << 31)) return fail(BLP_ERR_BAD_ARG, "%s: nnz = %lld set entries, at most 2^31 - 1", who, (long long)nnz);
+    if (row_base + N > (1ll << 31) || q_head + q_tail > (1ll << 31) / k)
+        return fail(BLP_ERR_BAD_ARG, "%s: global rows must stay below 2^31 and Q x k below 2^31", who);
+    if (!rows || !scores) return fail(BLP_ERR_BAD_ARG, "%s: NULL rows / scores", who);
+    const int64_t Q = q_head + q_tail;
+    if (Q > 0 && (!source || !fixed_row || !rel_id || !rel_emb || R <= 0 || S <= 0))
+        return fail(BLP_ERR_BAD_ARG, "%s: NULL source / fixed_row / rel_id / rel_emb, or R <= 0 / S <= 0", who);
+    if (Q > 0 && (G == 0 || !set_ptr || !qset_ptr_head || !qset_ptr_tail))
+        return fail(BLP_ERR_BAD_ARG, "%s: %lld queries but no set, or NULL set_ptr / qset_ptr_head / qset_ptr_tail", who, (long long)Q);
+    if (nnz > 0 && !set_row) return fail(BLP_ERR_BAD_ARG, "%s: %lld set entries but NULL set_row", who, (long long)nnz);
+    if (N > 0 && !table) return fail(BLP_ERR_BAD_ARG, "%s: NULL table", who);
+    if (!table_rows_aligned(table, BLP_DTYPE_F32, ld) || !aligned16(source) || (ld_src & 3) || ld_src < D || !aligned16(rel_emb))
+        return fail(BLP_ERR_BAD_ARG, "%s: table / source / rel_emb must be 16-byte aligned, ld %% 4 == 0, ld_src %% 4 == 0, ld_src >= D", who);
+    blp::FilterSpec spec;
+    if (filter) {
+        if (!filter->seg_lo || !filter->seg_hi || !filter->values || (filter->ent2idx && filter->ent2idx_len < 0))
+            return fail(BLP_ERR_BAD_ARG, "%s: filter needs seg_lo, seg_hi and values (ent2idx_len >= 0)", who);
+        if (filter->row_base != row_base)
+            return fail(BLP_ERR_BAD_ARG, "%s: filter row_base %lld differs from the call's row_base %lld", who,
+                        (long long)filter->row_base, (long long)row_base);
+        spec.lo = filter->seg_lo; spec.hi = filter->seg_hi; spec.val = filter->values; spec.exclude = filter->exclude;
+        spec.ent2idx = filter->ent2idx; spec.ent2idx_len = filter->ent2idx ? filter->ent2idx_len : 0;
+        spec.row_base = filter->row_base;
+    }
+    if (Q == 0) return BLP_OK;
+    const size_t need = blp::topk_sets_workspace_bytes(model, D, q_head, q_tail, G, nnz, k);
+    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255u))
+        return fail(BLP_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned and >= %zu bytes (got %zu)", who, need, workspace_bytes);
+    DeviceGuard guard(device);
+    if (guard.error() != hipSuccess) return hip_fail(guard.error(), "hipSetDevice");
+    int cu = 0;
+    if (int rc = compute_units(device, &cu)) return rc;
+    const blp::SetLookup sets{set_ptr, set_row, qset_ptr_head, qset_ptr_tail, G, row_base};
+    hipError_t err = blp::launch_topk_sets(model, D, table, N, ld, blp::QRows::rows_of(source, fixed_row, ld_src),
+                                           blp::QRows::rows_of(rel_emb, rel_id, D), q_head, q_tail, k, sets, nnz, spec, rows, scores,
+                                           workspace, cu, static_cast<hipStream_t>(stream));
+    if (err != hipSuccess) return hip_fail(err, "blp_topk_sets launch");
+    return BLP_OK;
 }
 
 // ---- re-ranking a retrieval run (rerank.hip)

@@ -23,6 +23,7 @@ enum Knob : int {
     KNOB_INBATCH_PROBE,          // timing probe of the in-batch loss forward (wrong results!): bit 0: no index workgroups; bit 1: no tickets / final sum; bit 2: no redundant positives
     KNOB_INBATCH_SHARES,         // waves per entity row of the in-batch loss backward (a power of two <= 16; 0: by batch size)
     KNOB_RANK_SETS_GRID,         // workgroups of rank_sets_kernel's persistent grid (rank_sets.hip; 0: three per compute unit)
+    KNOB_TOPK_SETS_GRID,         // workgroups of topk_sets_kernel's persistent grid (topk_sets.hip; 0: by the kernel's residency per compute unit)
     KNOB_COUNT
 };
 

@@ -99,6 +99,13 @@ hipError_t launch_topk(int model, int D, int dtype, const void* table, int64_t N
 hipError_t launch_topk_merge(const int64_t* rows, const float* scores, int64_t Q, int64_t n_in, int k, int64_t* rows_out,
                              float* scores_out, hipStream_t stream);
 
+// topk.hip's second and third stage for topk_sets.hip: the k best of (Q, n_in) keys (topk_lists.h; 0 = an empty slot) ->
+// rows / scores, and the winners of an f32 table re-scored by Scorer<>::score<true>
+hipError_t launch_topk_merge_keys(const unsigned long long* keys, int64_t Q, int64_t n_in, int k, int64_t* rows_out, float* scores_out,
+                                  hipStream_t stream);
+hipError_t launch_topk_rescore(int model, int D, const float* table, int64_t ld, int64_t row_base, const QRows q_fixed, const QRows q_rel,
+                               int64_t q_head, int64_t Q, int k, const int64_t* rows, float* scores, hipStream_t stream);
+
 // rank_lists.hip: counts and scores of per-query candidate lists (include/blp_hip.h: blp_rank_lists); q_true.base == nullptr
 // with counts == nullptr: scores only.  The workspace holds the true keys (needed with counts only).
 bool rank_lists_supported(int model, int dtype, int D);

@@ -44,24 +44,11 @@
 #include "score_core.h"
 #include "table_elem.h"
 #include "tile.h"
+#include "topk_lists.h"
 
 #pragma clang fp contract(off)
 
 namespace blp {
-
-typedef unsigned long long u64;
-
-constexpr int kTopkWaves = 4;               // waves per workgroup of topk_tiles
-constexpr int kTopkMaxChunk = 32;           // queries per workgroup
-constexpr int kTopkListBytes = 24576;       // LDS for the lists of one workgroup (kTopkWaves x chunk x k keys)
-constexpr int kTopkTargetGroups = 512;      // workgroups of topk_tiles when the queries alone give fewer
-constexpr int kTopkMaxK = 256;
-constexpr int kTopkMergeMaxWaves = 16;
-
-__host__ __device__ inline int topk_chunk(int k) {
-    const int c = kTopkListBytes / (kTopkWaves * 8 * k);
-    return c < 1 ? 1 : (c > kTopkMaxChunk ? kTopkMaxChunk : c);
-}
 
 // candidate slabs per query chunk: n_slabs x n_chunks <= max(n_chunks, kTopkTargetGroups), and at most one per kTopkWaves tiles
 static int64_t topk_slabs(int64_t N, int64_t Q, int k) {
@@ -71,68 +58,6 @@ static int64_t topk_slabs(int64_t N, int64_t Q, int k) {
     const int64_t cap = (tiles + kTopkWaves - 1) / kTopkWaves;
     if (s > cap) s = cap;
     return s < 1 ? 1 : s;
-}
-
-__device__ __forceinline__ u64 topk_key(float s, int64_t row) {
-    unsigned b = __float_as_uint(s);
-    const unsigned neg0 = b == 0x80000000u;
-    unsigned hi;
-    if (__builtin_isnan(s)) {
-        hi = 1u;
-    } else {
-        if (neg0) b = 0u;
-        hi = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    }
-    const unsigned lo = ((0x7fffffffu - (unsigned)row) << 1) | neg0;
-    return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ int64_t key_row(u64 key) { return key ? (int64_t)(0x7fffffffu - ((unsigned)key >> 1)) : -1; }
-__device__ __forceinline__ float key_score(u64 key) {
-    const unsigned hi = (unsigned)(key >> 32);
-    if (hi <= 1u) return __uint_as_float(0x7fc00000u);
-    unsigned b = (hi & 0x80000000u) ? (hi & 0x7fffffffu) : ~hi;
-    if (key & 1ull) b = 0x80000000u;
-    return __uint_as_float(b);
-}
-
-// Insert x (wave-uniform) into the list L[0, n) in LDS, sorted descending, dropping its last entry.  Lane l moves slots
-// l, l + 64, ... (n <= kTopkMaxK: four per lane, statically indexed).
-__device__ __forceinline__ void list_insert(u64* L, int n, u64 x, int lane) {
-    u64 nv[kTopkMaxK / 64];
-    static_for<kTopkMaxK / 64>([&](auto jj) {
-        constexpr int j = decltype(jj)::value;
-        const int p = lane + 64 * j;
-        if (p < n) {
-            const u64 old = L[p];
-            const u64 prev = p > 0 ? L[p - 1] : ~0ull;
-            nv[j] = old > x ? old : (prev > x ? x : prev);
-        }
-    });
-    wave_lds_sync();
-    static_for<kTopkMaxK / 64>([&](auto jj) {
-        constexpr int j = decltype(jj)::value;
-        const int p = lane + 64 * j;
-        if (p < n) L[p] = nv[j];
-    });
-    wave_lds_sync();
-}
-
-// Offer the wave's 64 keys (one per lane; 0 = none) to the list L[0, n): lanes above its last entry, minus those
-// drop(mask) removes, are inserted.
-template <class Drop>
-__device__ __forceinline__ void list_offer(u64* L, int n, u64 key, int lane, Drop drop) {
-    u64 thr = L[n - 1];
-    u64 mask = __ballot(key > thr);
-    if (!mask) return;
-    mask = drop(mask);
-    while (mask) {
-        const int b = __builtin_ctzll(mask);
-        mask &= mask - 1;
-        const u64 x = __shfl(key, b);
-        if (x <= thr) continue;
-        list_insert(L, n, x, lane);
-        thr = L[n - 1];
-    }
 }
 
 // The lanes of `mask` whose candidate (table row row0 + lane) query q's filter segment does NOT remove: the segment is
@@ -428,6 +353,29 @@ static hipError_t launch_merge(const u64* keys, const int64_t* rows_in, const fl
 hipError_t launch_topk_merge(const int64_t* rows, const float* scores, int64_t Q, int64_t n_in, int k, int64_t* rows_out,
                              float* scores_out, hipStream_t stream) {
     return launch_merge(nullptr, rows, scores, Q, n_in, k, rows_out, scores_out, stream);
+}
+
+// topk_sets.hip: the second and third stage of a call on its own partial lists -- keys (Q, n_in), 0 = an empty slot
+hipError_t launch_topk_merge_keys(const unsigned long long* keys, int64_t Q, int64_t n_in, int k, int64_t* rows_out, float* scores_out,
+                                  hipStream_t stream) {
+    return launch_merge(keys, nullptr, nullptr, Q, n_in, k, rows_out, scores_out, stream);
+}
+
+hipError_t launch_topk_rescore(int model, int D, const float* table, int64_t ld, int64_t row_base, const QRows q_fixed, const QRows q_rel,
+                               int64_t q_head, int64_t Q, int k, const int64_t* rows, float* scores, hipStream_t stream) {
+    const int64_t slots = Q * k;
+    if (slots == 0) return hipSuccess;
+#define BLP_RESCORE_CASE(M, DD)                                                                                                   \
+    if (model == M && D == DD) {                                                                                                  \
+        topk_rescore_kernel<M, DD, float><<<dim3((unsigned)((slots + 63) / 64)), 64, 0, stream>>>(table, ld, row_base, q_fixed, q_rel, \
+                                                                                                  q_head, Q, k, rows, scores);   \
+        return hipGetLastError();                                                                                                 \
+    }
+#define BLP_RESCORE_MODEL(M) BLP_RESCORE_CASE(M, 64) BLP_RESCORE_CASE(M, 128) BLP_RESCORE_CASE(M, 256)
+    BLP_RESCORE_MODEL(TRANSE) BLP_RESCORE_MODEL(DISTMULT) BLP_RESCORE_MODEL(COMPLEX) BLP_RESCORE_MODEL(SIMPLE)
+#undef BLP_RESCORE_MODEL
+#undef BLP_RESCORE_CASE
+    return hipErrorInvalidValue;
 }
 
 template <int MODEL, int D, class T>

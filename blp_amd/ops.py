@@ -6,6 +6,7 @@ device memory and the stream; every arithmetic step of the hot path runs in the 
     topk(...)           filtered top-k prediction per query (no score matrix)
     rank_lists(...)     counts / scores of per-query candidate lists (only the listed rows are read)
     rank_sets(...)      counts against candidate sets shared by groups of queries (type-constrained evaluation)
+    topk_sets(...)      filtered top-k prediction inside candidate sets shared by groups of queries
     rerank_cosine(...)  cosine of every retrieval candidate with its query (retrieval.py:170-175)
     rerank_ndcg(...)    trec_eval ndcg_cut of every (alpha, query) of a re-ranked run (retrieval.py:139-258)
     score(...)          score_fn(heads, tails, rels)       (models.py:222-248), differentiable
@@ -564,6 +565,80 @@ def rank_sets(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, tru
     if status:
         _lib.check(status, "blp_rank_sets_typed" if tdt else "blp_rank_sets")
     return counts
+
+
+def topk_sets_supported(rel_model, dim, k):
+    """True if topk_sets takes this width and k (include/blp_hip.h: blp_topk_sets_supported -- the four models at 64 / 128 /
+    256, 1 <= k <= 256; a float32 table)."""
+    return bool(_lib.lib().blp_topk_sets_supported(_lib.MODEL_IDS[rel_model], int(dim), int(k)))
+
+
+def topk_sets_workspace_bytes(rel_model, D, q_head, q_tail, num_sets, nnz, k):
+    """Bytes of topk_sets' workspace: it depends on the queries, the number of sets, k and (boundedly) the number of set
+    entries -- never on the table's length."""
+    return int(_lib.lib().blp_topk_sets_workspace_bytes(_lib.MODEL_IDS[rel_model], int(D), int(q_head), int(q_tail), int(num_sets),
+                                                        int(nnz), int(k)))
+
+
+def topk_sets(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, set_ptr, set_rows, qset_ptr_head, qset_ptr_tail,
+              filter=None, row_base=0, out=None):
+    """Filtered top-k prediction inside candidate sets that queries SHARE (blp_topk_sets).  Queries, sets and grouping as in
+    rank_sets -- head-replacing [0, q_head), then tail-replacing; fixed_row (Q,) indexes ``source`` (S, D) float32, rel_ids
+    (Q,) index ``rel_emb`` (R, D); within each side GROUPED by set: set g serves head queries [qset_ptr_head[g],
+    qset_ptr_head[g + 1]) and tail queries q_head + [qset_ptr_tail[g], qset_ptr_tail[g + 1]); set g is entries [set_ptr[g],
+    set_ptr[g + 1]) of ``set_rows`` (nnz,): GLOBAL rows of ``table`` (N, D) float32 -- which holds global rows [row_base,
+    row_base + N) --, strictly ascending within a set; entries outside the shard are skipped.  The output is topk's, taken over
+    the query's set: the k entries with the highest score_fn value (descending score, ties by ascending row, NaN last), the
+    rows ``filter`` (a SegmentFilter whose row_base is ``row_base``) names removed; slots beyond the entries left: row -1,
+    score NaN.  Returns (rows (Q, k) int64, scores (Q, k) float32) in the caller's (grouped) order; ``out`` may give both."""
+    _require_device(table, source, fixed_row, rel_emb, rel_ids, set_ptr, set_rows, qset_ptr_head, qset_ptr_tail)
+    if table.dtype != torch.float32:
+        raise TypeError(f"topk_sets reads a float32 table, got {table.dtype}")
+    same = source is table
+    table = _f32_rows(table, "table")
+    source = table if same else _f32_rows(source, "source")
+    rel_emb = _f32_rows(rel_emb, "rel_emb").contiguous()
+    N, D = table.shape
+    if source.dim() != 2 or source.shape[1] != D:
+        raise ValueError(f"source must be (S, {D}), got {tuple(source.shape)}")
+    fixed_row, rel_ids = _i64_vector(fixed_row), _i64_vector(rel_ids)
+    set_ptr, set_rows = _i64_vector(set_ptr), _i64_vector(set_rows)
+    qset_ptr_head, qset_ptr_tail = _i64_vector(qset_ptr_head), _i64_vector(qset_ptr_tail)
+    Q, nnz, G = fixed_row.shape[0], set_rows.shape[0], set_ptr.shape[0] - 1
+    k = int(k)
+    if rel_ids.shape[0] != Q or rel_emb.dim() != 2 or rel_emb.shape[1] != D:
+        raise ValueError("fixed_row and rel_ids need one entry per query; rel_emb must be (R, D)")
+    if G < 0 or qset_ptr_head.shape[0] != G + 1 or qset_ptr_tail.shape[0] != G + 1:
+        raise ValueError("set_ptr, qset_ptr_head and qset_ptr_tail need G + 1 entries each")
+    if not 0 <= q_head <= Q:
+        raise ValueError(f"q_head = {q_head} outside [0, {Q}]")
+    if not topk_sets_supported(rel_model, D, k):
+        raise ValueError(f"topk_sets: D = {D}, k = {k} not supported (D in 64 / 128 / 256, 1 <= k <= 256): see topk_sets_supported")
+    if filter is not None and int(filter.row_base) != int(row_base):
+        raise ValueError(f"topk_sets: the filter's row_base {filter.row_base} differs from row_base {row_base}")
+    dev = table.device
+    if out is None:
+        out = (torch.empty((Q, k), dtype=torch.int64, device=dev), torch.empty((Q, k), dtype=torch.float32, device=dev))
+    rows, scores = out
+    if rows.shape != (Q, k) or rows.dtype != torch.int64 or not rows.is_contiguous() or scores.shape != (Q, k) or \
+            scores.dtype != torch.float32 or not scores.is_contiguous():
+        raise ValueError("out must be contiguous (Q, k) int64 rows and (Q, k) float32 scores")
+    if Q == 0:
+        return rows, scores
+    L = _lib.lib()
+    model = _lib.MODEL_IDS[rel_model]
+    stream = torch._C._cuda_getCurrentRawStream(dev.index)
+    ws_bytes = L.blp_topk_sets_workspace_bytes(model, D, q_head, Q - q_head, G, nnz, k)
+    workspace = _workspace(dev, stream, ws_bytes)
+    spec = None if filter is None else _filter_spec(filter, Q, dev)
+    status = L.blp_topk_sets(model, table.data_ptr(), N, D, table.stride(0) if N > 1 else D, int(row_base), source.data_ptr(),
+                             source.shape[0], source.stride(0) if source.shape[0] > 1 else D, fixed_row.data_ptr(), rel_emb.data_ptr(),
+                             rel_emb.shape[0], rel_ids.data_ptr(), q_head, Q - q_head, k, set_ptr.data_ptr(),
+                             _addr(set_rows) if nnz else None, nnz, G, qset_ptr_head.data_ptr(), qset_ptr_tail.data_ptr(), spec,
+                             rows.data_ptr(), scores.data_ptr(), workspace.data_ptr(), ws_bytes, dev.index, stream)
+    if status:
+        _lib.check(status, "blp_topk_sets")
+    return rows, scores
 
 
 def topk_merge(rows, scores, k):

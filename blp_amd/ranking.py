@@ -912,6 +912,19 @@ def _rank_sets_dense(score_fn, table, fixed, rel, true_vec, q_head, set_ptr, set
     return acc.to(torch.int32)
 
 
+def _group_by_set(set_ids, q_head, num_sets):
+    """The queries of each side grouped by set (stable: a group keeps the caller's order): (perm (Q,), qptr_head (G + 1,),
+    qptr_tail (G + 1,)) -- grouped query i is the caller's query perm[i]; the runs as blp_rank_sets takes them."""
+    device = set_ids.device
+    order_h = torch.sort(set_ids[:q_head], stable=True).indices
+    order_t = torch.sort(set_ids[q_head:], stable=True).indices + q_head
+    qptr_head = torch.zeros(num_sets + 1, dtype=torch.long, device=device)
+    qptr_tail = torch.zeros(num_sets + 1, dtype=torch.long, device=device)
+    qptr_head[1:] = torch.cumsum(torch.bincount(set_ids[:q_head], minlength=num_sets), 0)
+    qptr_tail[1:] = torch.cumsum(torch.bincount(set_ids[q_head:], minlength=num_sets), 0)
+    return torch.cat((order_h, order_t)), qptr_head, qptr_tail
+
+
 def rank_in_sets(model, table, triples, sets, ent2idx, *, set_ids=None, side="both", filter_index=None, add_true=True):
     """Rank every triple's true entity against a candidate SET that it shares with other queries -- type-constrained
     evaluation (the default: a head query of relation r against set r, a tail query against set R + r of
@@ -965,14 +978,7 @@ def rank_in_sets(model, table, triples, sets, ent2idx, *, set_ids=None, side="bo
         raise ValueError(f"set_ids needs one entry per query ({Q}), got {set_ids.shape[0]}")
     if Q and (int(set_ids.min()) < 0 or int(set_ids.max()) >= G):
         raise ValueError(f"rank_in_sets: a set id outside [0, {G})")
-    # the queries of each side grouped by set (stable: a group keeps the caller's order)
-    order_h = torch.sort(set_ids[:q_head], stable=True).indices
-    order_t = torch.sort(set_ids[q_head:], stable=True).indices + q_head
-    perm = torch.cat((order_h, order_t))
-    qptr_head = torch.zeros(G + 1, dtype=torch.long, device=device)
-    qptr_tail = torch.zeros(G + 1, dtype=torch.long, device=device)
-    qptr_head[1:] = torch.cumsum(torch.bincount(set_ids[:q_head], minlength=G), 0)
-    qptr_tail[1:] = torch.cumsum(torch.bincount(set_ids[q_head:], minlength=G), 0)
+    perm, qptr_head, qptr_tail = _group_by_set(set_ids, q_head, G)
     g_fixed, g_true, g_rel = fixed_rows[perm], true_rows[perm], rel_ids[perm]
     filt = None
     if filter_index is not None and Q:
@@ -1004,6 +1010,127 @@ def rank_in_sets(model, table, triples, sets, ent2idx, *, set_ids=None, side="bo
         counts[:, 1] += absent.to(torch.int32)
         counts[:, 3] += absent.to(torch.int32)
     return counts
+
+
+# ----------------------------------------------------------------------------------- link prediction inside candidate sets
+def _topk_sets_dense(score_fn, table, fixed, rel, q_head, k, set_ptr, set_rows, qptr_head, qptr_tail, row_base, filt,
+                     max_bytes=1 << 28):
+    """The dense route of predict_links_in_sets: score_fn of each set's gathered rows against its group's queries, in (query
+    chunk, row slab) pieces of bounded bytes, the filter through _filtered_pairs, the order by _stable_topk.  Queries grouped by
+    set within each side, as blp_topk_sets takes them; fixed / rel (Q, D) float32.  CPU tensors and the widths and table dtypes
+    blp_topk_sets does not take; on CPU tensors it is the oracle of the fused route.  Returns (rows (Q, k) int64 global rows,
+    scores (Q, k) float32)."""
+    Q, (N, D) = fixed.shape[0], table.shape
+    dev = table.device
+    rows_out = torch.full((Q, k), -1, dtype=torch.int64, device=dev)
+    scores_out = torch.full((Q, k), float("nan"), dtype=torch.float32, device=dev)
+    budget = max(1, max_bytes // (12 * D))  # (row, query) pairs per piece: three (pairs, D) float32 operands
+    sp, qh, qt = set_ptr.tolist(), qptr_head.tolist(), qptr_tail.tolist()
+    for g in range(len(sp) - 1):
+        local = set_rows[sp[g]:sp[g + 1]] - row_base
+        local = local[(local >= 0) & (local < N)]
+        n = local.shape[0]
+        runs = [(head, a, b) for head, a, b in ((True, qh[g], qh[g + 1]), (False, q_head + qt[g], q_head + qt[g + 1])) if a < b]
+        if not n or not runs:
+            continue
+        step = max(1, budget // n)  # queries per piece; a set longer than the budget goes through in row slabs
+        slab = max(1, budget // step)
+        for head, a, b in runs:
+            for lo in range(a, b, step):
+                hi = min(lo + step, b)
+                c = hi - lo
+                s = torch.empty((c, n), dtype=torch.float32, device=dev)
+                for r0 in range(0, n, slab):
+                    e = table[local[r0:r0 + slab]].float()
+                    m = e.shape[0]
+                    ee = e.unsqueeze(0).expand(c, m, D).reshape(c * m, D)
+                    ff = fixed[lo:hi].unsqueeze(1).expand(c, m, D).reshape(c * m, D)
+                    rr = rel[lo:hi].unsqueeze(1).expand(c, m, D).reshape(c * m, D)
+                    s[:, r0:r0 + m] = (score_fn(ee, ff, rr) if head else score_fn(ff, ee, rr)).reshape(c, m)
+                removed = torch.zeros((c, n), dtype=torch.bool, device=dev)
+                f_owner, f_local = _filtered_pairs(filt, lo, hi, row_base, N, dev)
+                if f_owner.numel():
+                    pos = torch.searchsorted(local, f_local).clamp(max=n - 1)
+                    hit = local[pos] == f_local
+                    removed[f_owner[hit], pos[hit]] = True
+                rows_out[lo:hi], scores_out[lo:hi] = _stable_topk(s, (local + row_base).expand(c, n), removed, k)
+    return rows_out, scores_out
+
+
+def predict_links_in_sets(model, table, triples, k, sets, ent2idx, *, set_ids=None, side="both", filter_index=None,
+                          entities=None):
+    """predict_links inside candidate SETS that queries share: for every triple (head, tail, rel) of ``triples`` (T, 3) the k
+    rows of the query's set the model scores highest as the replaced entity -- "the 10 best tails of (h, r, ?) among the
+    entities that can be a tail of r" (the default: a head query of relation r answers from set r, a tail query from set
+    R + r of relation_candidate_sets), a first-stage pool re-ranked for a group of queries, per-language pools.
+    triples      ``side`` "head": (?, r, t); "tail": (h, r, ?); "both": Q = 2 T queries in predict_links' order [heads | tails]
+    sets         CandidateSets of table rows; set_ids (Q,) the set of every query, in that order (rank_in_sets' arguments)
+    ent2idx      utils.make_ent2idx map (entity id -> table row); the fixed entity of every query must have a row
+    filter_index utils.FilterIndex of the known edges: the rows it names are removed, not demoted (the entity at the replaced
+                 position is never removed: pass -1 there to have every known edge filtered)
+    entities     optional (num_entities,) entity id of every table row: ids instead of rows are returned
+    Returns predict_links' result, (rows or ids (Q, k) int64, scores (Q, k) float32) in the caller's order: descending score,
+    ties by ascending row, NaN last; -1 / NaN beyond the entries of the set that are left.  Scores are score_fn's values bit
+    for bit.  A float32 HIP table at 64 / 128 / 256 and k <= 256 goes through blp_topk_sets (a row of a set is fetched once per
+    chunk of its group's queries); CPU tensors, other widths and 16-bit tables take the dense route: score_fn on gathered
+    rows and a stable sort."""
+    model = _module(model)
+    if side not in ("head", "tail", "both"):
+        raise ValueError(f"side must be 'head', 'tail' or 'both', got {side!r}")
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"k = {k} must be >= 1")
+    device = table.device
+    N, D = table.shape
+    triples = triples.to(device=device, dtype=torch.long).reshape(-1, 3)
+    ent2idx = ent2idx.to(device=device, dtype=torch.long)
+    T = triples.shape[0]
+    h, t, r = triples[:, 0], triples[:, 1], triples[:, 2]
+    heads, tails = side in ("head", "both"), side in ("tail", "both")
+    q_head = T if heads else 0
+    fixed_ids = torch.cat([x for x, on in ((t, heads), (h, tails)) if on])
+    rel_ids = torch.cat([r] * (int(heads) + int(tails)))
+    Q = fixed_ids.shape[0]
+    known = (fixed_ids >= 0) & (fixed_ids < ent2idx.shape[0])
+    fixed_rows = torch.where(known, ent2idx[torch.where(known, fixed_ids, torch.zeros_like(fixed_ids))], torch.full_like(fixed_ids, -1))
+    rel_w = model.rel_emb.weight.detach()
+    R = rel_w.shape[0]
+    if Q and bool(((fixed_rows < 0) | (fixed_rows >= N) | (rel_ids < 0) | (rel_ids >= R)).any()):
+        raise ValueError("predict_links_in_sets: a query's fixed entity has no table row, or its relation is out of range")
+    set_ptr, set_rows = sets.ptr.to(device), sets.rows.to(device)
+    G = set_ptr.shape[0] - 1
+    if set_rows.numel() and int(set_rows.max()) >= N:
+        raise ValueError(f"predict_links_in_sets: the sets name row {int(set_rows.max())}, the table has {N} rows")
+    if set_ids is None:
+        set_ids = torch.cat([x for x, on in ((r, heads), (r + R, tails)) if on])
+    set_ids = set_ids.to(device=device, dtype=torch.long).reshape(-1)
+    if set_ids.shape[0] != Q:
+        raise ValueError(f"set_ids needs one entry per query ({Q}), got {set_ids.shape[0]}")
+    if Q and (int(set_ids.min()) < 0 or int(set_ids.max()) >= G):
+        raise ValueError(f"predict_links_in_sets: a set id outside [0, {G})")
+    if Q == 0:
+        return torch.empty((0, k), dtype=torch.int64, device=device), torch.empty((0, k), dtype=torch.float32, device=device)
+    perm, qptr_head, qptr_tail = _group_by_set(set_ids, q_head, G)
+    g_fixed, g_rel = fixed_rows[perm], rel_ids[perm]
+    filt = None
+    if filter_index is not None:
+        seg = filter_index.segments(triples, ent2idx, device)
+        sel = torch.cat([x for x, on in ((torch.arange(T, device=device), heads), (torch.arange(T, 2 * T, device=device), tails)) if on])[perm]
+        filt = ops.SegmentFilter(seg.seg_lo[sel].contiguous(), seg.seg_hi[sel].contiguous(), seg.values,
+                                 seg.exclude[sel].contiguous(), seg.ent2idx, 0)
+    if table.is_cuda and table.dtype == torch.float32 and k <= 256 and ops.topk_sets_supported(model.rel_model, D, k):
+        g_rows, g_scores = ops.topk_sets(model.rel_model, table, table, g_fixed, rel_w, g_rel, q_head, k, set_ptr, set_rows,
+                                         qptr_head, qptr_tail, filter=filt)
+    else:
+        dense_filt = None if filt is None else (filt.seg_lo, filt.seg_hi, filt.values, filt.exclude, filt.ent2idx)
+        g_rows, g_scores = _topk_sets_dense(model.score_fn, table, table[g_fixed].float(), rel_w[g_rel], q_head, k, set_ptr,
+                                            set_rows, qptr_head, qptr_tail, 0, dense_filt)
+    rows, scores = torch.empty_like(g_rows), torch.empty_like(g_scores)
+    rows[perm], scores[perm] = g_rows, g_scores
+    if entities is not None:
+        entities = entities.to(device=device, dtype=torch.long)
+        rows = torch.where(rows >= 0, entities[rows.clamp(min=0)], rows)
+    return rows, scores
 
 
 def _module(model):

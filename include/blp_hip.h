@@ -598,6 +598,49 @@ int blp_rank_sets_typed(int model, const void *table, int table_dtype, int64_t N
                         size_t workspace_bytes, int device, void *stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Filtered top-k INSIDE candidate sets shared between queries: ANSWER a query (h, r, ?) / (?, r, t) with the k rows of ITS SET
+ * the model scores highest -- "the 10 best tails of (h, r, ?) among the entities that can be a tail of r", a first-stage
+ * pool re-ranked for a group of queries, per-language pools.  The contract is the union of blp_rank_sets' (queries, sets,
+ * grouping) and blp_topk's (output).  A row of a set is fetched once per (set, chunk of <= 32 queries of its group); no
+ * score is written out and nothing is sorted.
+ *
+ * Table: (N, D) f32, row stride ld -- GLOBAL rows [row_base, row_base + N).  Queries as in blp_rank_all_shard: Q = q_head +
+ * q_tail, head-replacing first; fixed_row indexes source (S, D) f32 (row stride ld_src), rel_id indexes rel_emb (R, D)
+ * contiguous.
+ * Sets and grouping exactly as in blp_rank_sets: set g owns entries [set_ptr[g], set_ptr[g + 1]) of set_row (nnz) int64
+ * GLOBAL rows, STRICTLY ASCENDING within a set; set_ptr (G + 1) int64 is trusted to be non-decreasing from 0 to nnz.  Within
+ * each side the queries are ordered by non-decreasing set: set g serves the head-replacing queries [qset_ptr_head[g],
+ * qset_ptr_head[g + 1]) and the tail-replacing queries q_head + [qset_ptr_tail[g], qset_ptr_tail[g + 1]) -- both (G + 1)
+ * int64, non-decreasing, from 0 to q_head / to q_tail.  A set may serve both sides, one side or no query.
+ * Output per query, k slots, in the caller's (grouped) query order: rows (Q, k) int64 global rows, scores (Q, k) f32 --
+ * blp_topk's output taken over the entries of the query's set that lie in [row_base, row_base + N):
+ *   scores are score_fn's values bit for bit (the torch-CPU order of oracle/blp_oracle.c, sign of zero included);
+ *   order: descending score by IEEE comparison, equal scores (-0 == +0) by ascending row, NaN after every number (by row);
+ *   filter (optional): a blp_filter with blp_rank_all's semantics whose row_base MUST equal this call's (else
+ *          BLP_ERR_BAD_ARG); filtered rows are REMOVED, not demoted; exclude[q] is never removed;
+ *   slots left over (an empty set, a set smaller than k, a filter that leaves fewer than k rows, a shard that holds fewer
+ *          than k of the set's rows): row -1, score NaN (the quiet NaN 0x7fc00000).
+ * Shards: an entry outside [row_base, row_base + N) is SKIPPED, so the per-shard results of several row_base shards, merged
+ * by blp_topk_merge, equal the unsharded call.
+ * Limits (blp_topk_sets_supported): the four models at D in {64, 128, 256}; 1 <= k <= 256; Q x k < 2^31; nnz < 2^31;
+ * row_base + N <= 2^31; table / source / rel_emb 16-byte aligned, ld % 4 == 0, ld_src % 4 == 0.
+ * Workspace: blp_topk_sets_workspace_bytes(model, D, q_head, q_tail, G, nnz, k) bytes, 256-B aligned: the queries'
+ * coefficient rows (2 D floats per query), G + 1 int64 of work-unit offsets and the partial lists of k 8-byte keys -- at most
+ * Q + 16 384 of them whatever nnz (long sets are cut into slabs only while the queries alone do not fill the device).  It
+ * does not depend on N and is <= 8 (D + k) Q + 8 (G + 1) + 4 MiB bytes.
+ * Asynchronous on `stream`, no host synchronisation, no allocation; nothing about set or group sizes is read on the host.
+ * Deterministic: a query's result is the set of its k largest keys, so nothing depends on the grid.
+ * (Added after 6.0.0 without a version change: no existing entry point changed.)
+ * -------------------------------------------------------------------------------------------- */
+int blp_topk_sets_supported(int model, int D, int k);
+size_t blp_topk_sets_workspace_bytes(int model, int D, int64_t q_head, int64_t q_tail, int64_t G, int64_t nnz, int k);
+int blp_topk_sets(int model, const float *table, int64_t N, int D, int64_t ld, int64_t row_base, const float *source, int64_t S,
+                  int64_t ld_src, const int64_t *fixed_row, const float *rel_emb, int64_t R, const int64_t *rel_id, int64_t q_head,
+                  int64_t q_tail, int k, const int64_t *set_ptr, const int64_t *set_row, int64_t nnz, int64_t G,
+                  const int64_t *qset_ptr_head, const int64_t *qset_ptr_tail, const blp_filter *filter, int64_t *rows,
+                  float *scores, void *workspace, size_t workspace_bytes, int device, void *stream);
+
+/* --------------------------------------------------------------------------------------------
  * Re-ranking a first-stage retrieval run (reference retrieval.py rerank: BM25F candidates of DBpedia-Entity v2 re-scored
  * with entity embeddings, the mixing weight alpha chosen per fold by nDCG@100).  Candidates are a CSR over Q queries:
  * query q owns candidates [cand_ptr[q], cand_ptr[q + 1]) (cand_ptr (Q + 1) int64, cand_ptr[0] = 0, cand_ptr[Q] = C).

@@ -1,0 +1,169 @@
+"""Time blp_topk_sets (filtered top-k inside candidate sets shared by groups of queries) next to what the library offered for
+the same job before it: blp_rank_lists with scores on the sets expanded into one list per query, followed by a device-side
+per-query stable top-k of those scores.
+
+For each workload: the same queries, sets and filter (tools/rank_sets_bench.py's workloads), k = 10; the expansion is done
+once, outside the timing (the lists of the expanded route are cut into calls of < 2^30 entries); rows and scores of the two
+routes must be equal before anything is timed.  The two routes alternate step by step in one process, each bracketed by
+device events; warm-up, then --steps steps; one JSON line with the median and p90 of both, their ratio, the share of the
+expanded route spent in blp_rank_lists, and the gather bandwidth of the new call (rows fetched: one per set entry and chunk of
+topk_chunk(k) = 32 queries of its group, D x 4 bytes each).
+
+    python tools/topk_sets_bench.py [--steps 30] [--warmup 3] [--only NAME ...] [--out profiles/topksets/topk_sets_bench.jsonl]
+
+  fb15k237-{transe,distmult}   105 740 queries, 14 541 x 128 table, 474 sets of 50 .. 8 000 rows (log-uniform)
+  longtable-transe             13 788 queries, 4.6 M x 128 table, 1 644 sets of 10^3 .. 10^6 rows (log-uniform)
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from blp_amd import ops  # noqa: E402
+from rank_sets_bench import FILTER_PER_QUERY, MAX_LIST_ENTRIES, WORKLOADS, measure, stats  # noqa: E402
+
+K = 10
+QUERY_CHUNK = 32  # topk_chunk(10)
+DEFAULT_OUT = os.path.join(ROOT, "profiles", "topksets", "topk_sets_bench.jsonl")
+
+
+def stable_topk_of_lists(scores, rows, removed, owner_local, ptr_local, n_queries, k):
+    """Per query the k best of its list by (score descending, -0 == +0, NaN last; ties by ascending row -- the lists are
+    ascending), removed entries dropped: three stable device sorts over the flat entries, then the first k of every segment."""
+    order = torch.sort(-scores, stable=True).indices                                     # descending; torch sorts NaN last
+    order = order[torch.sort(removed[order].to(torch.uint8), stable=True).indices]       # removed entries after everything
+    order = order[torch.sort(owner_local[order], stable=True).indices]                   # grouped by query, order kept
+    n_per = ptr_local[1:] - ptr_local[:-1]
+    left = n_per - torch.zeros_like(n_per).index_add_(0, owner_local, removed.to(n_per.dtype))
+    slot = torch.arange(k, device=scores.device).unsqueeze(0)
+    take = (ptr_local[:-1].unsqueeze(1) + slot).clamp(max=max(scores.shape[0] - 1, 0))
+    ok = slot < left.unsqueeze(1)
+    picked = order[take]
+    out_rows = torch.where(ok, rows[picked], torch.full_like(picked, -1))
+    out_scores = torch.where(ok, scores[picked], torch.full((n_queries, k), float("nan"), device=scores.device))
+    return out_rows, out_scores
+
+
+def run(name, cfg, steps, warmup):
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev).manual_seed(0)
+    rng = np.random.default_rng(0)
+    N, D, Q, G = cfg["N"], cfg["D"], cfg["Q"], cfg["G"]
+    table = torch.randn((N, D), generator=g, device=dev)
+    table = torch.nn.functional.normalize(table, dim=-1) if cfg["model"] == "transe" else table * 0.1
+    R = 237
+    rel_w = (torch.rand((R, D), generator=g, device=dev) - 0.5) * 0.25
+    sizes = np.exp(rng.uniform(np.log(cfg["set_min"]), np.log(cfg["set_max"]), G)).astype(np.int64)
+    set_ptr = torch.zeros(G + 1, dtype=torch.long, device=dev)
+    set_ptr[1:] = torch.cumsum(torch.from_numpy(sizes).to(dev), 0)
+    set_row = torch.cat([torch.randperm(N, generator=g, device=dev)[:int(n)].sort().values for n in sizes])
+    q_head = Q // 2
+    ids = torch.cat((torch.randint(0, G, (q_head,), generator=g, device=dev).sort().values,
+                     torch.randint(0, G, (Q - q_head,), generator=g, device=dev).sort().values))
+    qh = torch.zeros(G + 1, dtype=torch.long, device=dev)
+    qt = torch.zeros(G + 1, dtype=torch.long, device=dev)
+    qh[1:] = torch.cumsum(torch.bincount(ids[:q_head], minlength=G), 0)
+    qt[1:] = torch.cumsum(torch.bincount(ids[q_head:], minlength=G), 0)
+    fixed = torch.randint(0, N, (Q,), generator=g, device=dev)
+    rel_ids = torch.randint(0, R, (Q,), generator=g, device=dev)
+    n_per = (set_ptr[1:] - set_ptr[:-1])[ids]
+    first = set_ptr[ids]
+    # a value occurs once per filter segment: consecutive members of the set, distinct other rows, -1 where one of those is a
+    # listed member already (tools/rank_sets_bench.py's filter)
+    half = FILTER_PER_QUERY // 2
+    kk = torch.arange(half, device=dev).unsqueeze(0)
+    inside = set_row[first.unsqueeze(1) + (torch.randint(0, 1 << 30, (Q, 1), generator=g, device=dev) + kk) % n_per.unsqueeze(1)]
+    other = (torch.randint(0, N, (Q, 1), generator=g, device=dev) + kk * 3571) % N
+    other = torch.where((other.unsqueeze(2) == inside.unsqueeze(1)).any(2), torch.full_like(other, -1), other)
+    seg = torch.cat((inside, other), 1)
+    lo = torch.arange(Q, device=dev) * FILTER_PER_QUERY
+    filt = ops.SegmentFilter(lo, lo + FILTER_PER_QUERY, seg.reshape(-1).contiguous(), None, None, 0)
+    out = (torch.empty((Q, K), dtype=torch.int64, device=dev), torch.empty((Q, K), dtype=torch.float32, device=dev))
+
+    def fused():
+        ops.topk_sets(cfg["model"], table, table, fixed, rel_w, rel_ids, q_head, K, set_ptr, set_row, qh, qt, filter=filt, out=out)
+
+    # the expanded route: per-query lists in calls of at most MAX_LIST_ENTRIES entries, each of one side; what the filter
+    # removes is marked per entry once, outside the timing (blp_rank_lists' scores are unfiltered)
+    list_ptr_all = torch.zeros(Q + 1, dtype=torch.long, device=dev)
+    list_ptr_all[1:] = torch.cumsum(n_per, 0)
+    host_ptr = list_ptr_all.tolist()
+    calls, a = [], 0
+    while a < Q:
+        end = q_head if a < q_head else Q
+        b = a + 1
+        while b < end and host_ptr[b + 1] - host_ptr[a] <= MAX_LIST_ENTRIES:
+            b += 1
+        n = host_ptr[b] - host_ptr[a]
+        owner = torch.repeat_interleave(torch.arange(a, b, device=dev), n_per[a:b], output_size=n)
+        rows = set_row[first[owner] + torch.arange(host_ptr[a], host_ptr[b], device=dev) - list_ptr_all[owner]]
+        removed = torch.zeros(n, dtype=torch.bool, device=dev)
+        for j in range(FILTER_PER_QUERY):
+            removed |= rows == seg[owner, j]
+        calls.append((a, b, (list_ptr_all[a:b + 1] - host_ptr[a]).contiguous(), rows, removed, (owner - a).contiguous(),
+                      torch.empty(n, dtype=torch.float32, device=dev)))
+        del owner
+        a = b
+    exp_rows = torch.empty((Q, K), dtype=torch.int64, device=dev)
+    exp_scores = torch.empty((Q, K), dtype=torch.float32, device=dev)
+
+    def expanded_scores():
+        for a, b, ptr, rows, removed, owner, scores in calls:
+            ops.rank_lists(cfg["model"], table, table, fixed[a:b], rel_w, rel_ids[a:b], min(max(q_head - a, 0), b - a), ptr, rows,
+                           out=(None, scores))
+
+    def expanded():
+        expanded_scores()
+        for a, b, ptr, rows, removed, owner, scores in calls:
+            exp_rows[a:b], exp_scores[a:b] = stable_topk_of_lists(scores, rows, removed, owner, ptr, b - a, K)
+
+    fused()
+    expanded()
+    nan = torch.isnan(exp_scores)
+    same = bool(torch.equal(out[0], exp_rows)) and bool(torch.equal(torch.isnan(out[1]), nan)) and \
+        bool(torch.equal(out[1][~nan].view(torch.int32), exp_scores[~nan].view(torch.int32)))
+    if not same:
+        return {"workload": name, **cfg, "k": K, "results_equal": False}
+    ms = measure({"topk_sets": fused, "expanded_lists_topk": expanded, "expanded_lists_scores_only": expanded_scores}, steps, warmup)
+    s, e, sc = stats(ms["topk_sets"]), stats(ms["expanded_lists_topk"]), stats(ms["expanded_lists_scores_only"])
+    chunks = (torch.div(qh[1:] - qh[:-1] + QUERY_CHUNK - 1, QUERY_CHUNK, rounding_mode="floor") +
+              torch.div(qt[1:] - qt[:-1] + QUERY_CHUNK - 1, QUERY_CHUNK, rounding_mode="floor"))
+    fetched = int(((set_ptr[1:] - set_ptr[:-1]) * chunks).sum()) * D * 4
+    pairs = int(n_per.sum())
+    return {"workload": name, **cfg, "k": K, "set_entries": int(set_row.numel()), "pairs": pairs, "expanded_calls": len(calls),
+            "expanded_index_bytes": pairs * 8, "filter_entries_per_query": FILTER_PER_QUERY, "results_equal": same,
+            "topk_sets_ms": s, "expanded_lists_topk_ms": e, "expanded_lists_scores_only_ms": sc,
+            "expanded_over_topk_sets": round(e["median"] / s["median"], 2), "fetched_bytes": fetched,
+            "gather_TBps": round(fetched / (s["median"] * 1e-3) / 1e12, 3), "pairs_per_s": round(pairs / (s["median"] * 1e-3), 0),
+            "workspace_bytes": ops.topk_sets_workspace_bytes(cfg["model"], D, q_head, Q - q_head, G, int(set_row.numel()), K),
+            "steps": steps}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--only", nargs="*")
+    ap.add_argument("--out", default=DEFAULT_OUT)
+    args = ap.parse_args()
+    for name, cfg in WORKLOADS.items():
+        if args.only and name not in args.only:
+            continue
+        line = json.dumps(run(name, cfg, args.steps, args.warmup))
+        print(line, flush=True)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "a") as fh:
+                fh.write(line + "\n")
+        ops.release_workspaces()
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
