@@ -929,13 +929,15 @@ size_t blp_topk_sets_workspace_bytes(int model, int D, int64_t q_head, int64_t q
     return blp::topk_sets_workspace_bytes(model, D, q_head, q_tail, G, nnz, k);
 }
 
-int blp_topk_sets(int model, const float* table, int64_t N, int D, int64_t ld, int64_t row_base, const float* source, int64_t S,
-                  int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R, const int64_t* rel_id, int64_t q_head,
-                  int64_t q_tail, int k, const int64_t* set_ptr, const int64_t* set_row, int64_t nnz, int64_t G,
-                  const int64_t* qset_ptr_head, const int64_t* qset_ptr_tail, const blp_filter* filter, int64_t* rows, float* scores,
-                  void* workspace, size_t workspace_bytes, int device, void* stream) {
-    const char* who = "blp_topk_sets";
+// blp_topk_sets and blp_topk_sets_typed: the argument checks (messages under the entry's name `who`), then the launch
+static int topk_sets_call(const char* who, int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld,
+                          int64_t row_base, const float* source, int64_t S, int64_t ld_src, const int64_t* fixed_row,
+                          const float* rel_emb, int64_t R, const int64_t* rel_id, int64_t q_head, int64_t q_tail, int k,
+                          const int64_t* set_ptr, const int64_t* set_row, int64_t nnz, int64_t G, const int64_t* qset_ptr_head,
+                          const int64_t* qset_ptr_tail, const blp_filter* filter, int64_t* rows, float* scores, void* workspace,
+                          size_t workspace_bytes, int device, void* stream) {
     if (!valid_model(model)) return fail(BLP_ERR_BAD_ARG, "%s: unknown model %d", who, model);
+    if (!valid_table_dtype(table_dtype)) return fail(BLP_ERR_BAD_ARG, "%s: unknown table dtype %d", who, table_dtype);
     if (k < 1 || k > 256) return fail(BLP_ERR_BAD_ARG, "%s: k = %d outside [1, 256]", who, k);
     if (!blp_topk_sets_supported(model, D, k))
         return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (64 / 128 / 256: see blp_topk_sets_supported)", who, D);
@@ -953,8 +955,12 @@ int blp_topk_sets(int model, const float* table, int64_t N, int D, int64_t ld, i
         return fail(BLP_ERR_BAD_ARG, "%s: %lld queries but no set, or NULL set_ptr / qset_ptr_head / qset_ptr_tail", who, (long long)Q);
     if (nnz > 0 && !set_row) return fail(BLP_ERR_BAD_ARG, "%s: %lld set entries but NULL set_row", who, (long long)nnz);
     if (N > 0 && !table) return fail(BLP_ERR_BAD_ARG, "%s: NULL table", who);
-    if (!table_rows_aligned(table, BLP_DTYPE_F32, ld) || !aligned16(source) || (ld_src & 3) || ld_src < D || !aligned16(rel_emb))
-        return fail(BLP_ERR_BAD_ARG, "%s: table / source / rel_emb must be 16-byte aligned, ld %% 4 == 0, ld_src %% 4 == 0, ld_src >= D", who);
+    if (!table_rows_aligned(table, table_dtype, ld) || !aligned16(source) || (ld_src & 3) || ld_src < D || !aligned16(rel_emb))
+        return fail(BLP_ERR_BAD_ARG, table_dtype == BLP_DTYPE_F32
+                                         ? "%s: table / source / rel_emb must be 16-byte aligned, ld %% 4 == 0, ld_src %% 4 == 0, ld_src >= D"
+                                         : "%s: table / source / rel_emb must be 16-byte aligned, ld %% 8 == 0 (a 16-bit table's row stride, "
+                                           "in elements), ld_src %% 4 == 0, ld_src >= D",
+                    who);
     blp::FilterSpec spec;
     if (filter) {
         if (!filter->seg_lo || !filter->seg_hi || !filter->values || (filter->ent2idx && filter->ent2idx_len < 0))
@@ -975,11 +981,41 @@ int blp_topk_sets(int model, const float* table, int64_t N, int D, int64_t ld, i
     int cu = 0;
     if (int rc = compute_units(device, &cu)) return rc;
     const blp::SetLookup sets{set_ptr, set_row, qset_ptr_head, qset_ptr_tail, G, row_base};
-    hipError_t err = blp::launch_topk_sets(model, D, table, N, ld, blp::QRows::rows_of(source, fixed_row, ld_src),
+    hipError_t err = blp::launch_topk_sets(model, D, table_dtype, table, N, ld, blp::QRows::rows_of(source, fixed_row, ld_src),
                                            blp::QRows::rows_of(rel_emb, rel_id, D), q_head, q_tail, k, sets, nnz, spec, rows, scores,
                                            workspace, cu, static_cast<hipStream_t>(stream));
-    if (err != hipSuccess) return hip_fail(err, "blp_topk_sets launch");
+    if (err != hipSuccess) return hip_fail(err, table_dtype == BLP_DTYPE_F32 ? "blp_topk_sets launch" : "blp_topk_sets_typed launch");
     return BLP_OK;
+}
+
+int blp_topk_sets(int model, const float* table, int64_t N, int D, int64_t ld, int64_t row_base, const float* source, int64_t S,
+                  int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R, const int64_t* rel_id, int64_t q_head,
+                  int64_t q_tail, int k, const int64_t* set_ptr, const int64_t* set_row, int64_t nnz, int64_t G,
+                  const int64_t* qset_ptr_head, const int64_t* qset_ptr_tail, const blp_filter* filter, int64_t* rows, float* scores,
+                  void* workspace, size_t workspace_bytes, int device, void* stream) {
+    return topk_sets_call("blp_topk_sets", model, table, BLP_DTYPE_F32, N, D, ld, row_base, source, S, ld_src, fixed_row, rel_emb, R,
+                          rel_id, q_head, q_tail, k, set_ptr, set_row, nnz, G, qset_ptr_head, qset_ptr_tail, filter, rows, scores,
+                          workspace, workspace_bytes, device, stream);
+}
+
+int blp_topk_sets_typed_supported(int model, int table_dtype, int D, int k) {
+    return valid_model(model) && blp::topk_sets_typed_supported(model, table_dtype, D, k) ? 1 : 0;
+}
+
+size_t blp_topk_sets_typed_workspace_bytes(int model, int table_dtype, int D, int64_t q_head, int64_t q_tail, int64_t G, int64_t nnz,
+                                           int k) {
+    if (!blp_topk_sets_typed_supported(model, table_dtype, D, k)) return 0;
+    return blp_topk_sets_workspace_bytes(model, D, q_head, q_tail, G, nnz, k);
+}
+
+int blp_topk_sets_typed(int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld, int64_t row_base,
+                        const float* source, int64_t S, int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R,
+                        const int64_t* rel_id, int64_t q_head, int64_t q_tail, int k, const int64_t* set_ptr, const int64_t* set_row,
+                        int64_t nnz, int64_t G, const int64_t* qset_ptr_head, const int64_t* qset_ptr_tail, const blp_filter* filter,
+                        int64_t* rows, float* scores, void* workspace, size_t workspace_bytes, int device, void* stream) {
+    return topk_sets_call(table_dtype == BLP_DTYPE_F32 ? "blp_topk_sets" : "blp_topk_sets_typed", model, table, table_dtype, N, D, ld,
+                          row_base, source, S, ld_src, fixed_row, rel_emb, R, rel_id, q_head, q_tail, k, set_ptr, set_row, nnz, G,
+                          qset_ptr_head, qset_ptr_tail, filter, rows, scores, workspace, workspace_bytes, device, stream);
 }
 
 // ---- re-ranking a retrieval run (rerank.hip)

@@ -105,6 +105,10 @@ hipError_t launch_topk_merge_keys(const unsigned long long* keys, int64_t Q, int
                                   hipStream_t stream);
 hipError_t launch_topk_rescore(int model, int D, const float* table, int64_t ld, int64_t row_base, const QRows q_fixed, const QRows q_rel,
                                int64_t q_head, int64_t Q, int k, const int64_t* rows, float* scores, hipStream_t stream);
+// ... of a table of any storage type (dtype: table_elem.h; ld in elements), re-scored on the rows widened to f32
+hipError_t launch_topk_rescore_typed(int model, int D, int dtype, const void* table, int64_t ld, int64_t row_base, const QRows q_fixed,
+                                     const QRows q_rel, int64_t q_head, int64_t Q, int k, const int64_t* rows, float* scores,
+                                     hipStream_t stream);
 
 // rank_lists.hip: counts and scores of per-query candidate lists (include/blp_hip.h: blp_rank_lists); q_true.base == nullptr
 // with counts == nullptr: scores only.  The workspace holds the true keys (needed with counts only).

@@ -132,13 +132,15 @@ hipError_t launch_rank_sets(int model, int D, int dtype, const void* table, int6
                             const QRows q_rel, const QRows q_true, int64_t q_head, int64_t q_tail, const SetLookup& sets, int64_t nnz,
                             const FilterSpec& filter, int32_t* counts, void* workspace, int n_cu, hipStream_t stream);
 
-// topk_sets.hip: filtered top-k inside candidate sets shared between queries (include/blp_hip.h: blp_topk_sets); an f32 table;
-// the workspace holds the coefficient rows, the G + 1 values of the unit prefix and the (Q, S_max, k) partial lists
+// topk_sets.hip: filtered top-k inside candidate sets shared between queries (include/blp_hip.h: blp_topk_sets,
+// blp_topk_sets_typed); the table f32 or 16-bit (dtype: table_elem.h; ld in elements); the workspace -- the same for every
+// dtype -- holds the coefficient rows, the G + 1 values of the unit prefix and the (Q, S_max, k) partial lists
 bool topk_sets_supported(int model, int D, int k);
+bool topk_sets_typed_supported(int model, int dtype, int D, int k);
 size_t topk_sets_workspace_bytes(int model, int D, int64_t q_head, int64_t q_tail, int64_t G, int64_t nnz, int k);
-hipError_t launch_topk_sets(int model, int D, const float* table, int64_t N, int64_t ld, const QRows q_fixed, const QRows q_rel,
-                            int64_t q_head, int64_t q_tail, int k, const SetLookup& sets, int64_t nnz, const FilterSpec& filter,
-                            int64_t* rows, float* scores, void* workspace, int n_cu, hipStream_t stream);
+hipError_t launch_topk_sets(int model, int D, int dtype, const void* table, int64_t N, int64_t ld, const QRows q_fixed,
+                            const QRows q_rel, int64_t q_head, int64_t q_tail, int k, const SetLookup& sets, int64_t nnz,
+                            const FilterSpec& filter, int64_t* rows, float* scores, void* workspace, int n_cu, hipStream_t stream);
 
 // ---- the bounded worst case of the pre-pass paths (round 5) --------------------------------------------------------------
 // A pre-pass pays off while it leaves little to the exact path.  When a device-side counter says it has not -- the pair lists

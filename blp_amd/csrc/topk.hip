@@ -378,6 +378,41 @@ hipError_t launch_topk_rescore(int model, int D, const float* table, int64_t ld,
     return hipErrorInvalidValue;
 }
 
+// launch_topk_rescore for a table of any storage type (dtype: table_elem.h; ld in elements): the winners re-scored on the
+// rows widened to f32 -- the instantiations of topk_rescore_kernel that topk_impl launches, no kernel of its own
+template <int MODEL, int D, class T>
+static hipError_t rescore_impl(const T* table, int64_t ld, int64_t row_base, const QRows& q_fixed, const QRows& q_rel, int64_t q_head,
+                               int64_t Q, int k, const int64_t* rows, float* scores, hipStream_t stream) {
+    const int64_t slots = Q * k;
+    topk_rescore_kernel<MODEL, D, T><<<dim3((unsigned)((slots + 63) / 64)), 64, 0, stream>>>(table, ld, row_base, q_fixed, q_rel,
+                                                                                             q_head, Q, k, rows, scores);
+    return hipGetLastError();
+}
+
+hipError_t launch_topk_rescore_typed(int model, int D, int dtype, const void* table, int64_t ld, int64_t row_base, const QRows q_fixed,
+                                     const QRows q_rel, int64_t q_head, int64_t Q, int k, const int64_t* rows, float* scores,
+                                     hipStream_t stream) {
+    if (dtype == kTableF32)
+        return launch_topk_rescore(model, D, static_cast<const float*>(table), ld, row_base, q_fixed, q_rel, q_head, Q, k, rows, scores,
+                                   stream);
+    if (Q * k == 0) return hipSuccess;
+#define BLP_RESCORE16_CASE(M, DD)                                                                                                  \
+    if (model == M && D == DD) {                                                                                                   \
+        if (dtype == kTableF16)                                                                                                    \
+            return rescore_impl<M, DD>(static_cast<const _Float16*>(table), ld, row_base, q_fixed, q_rel, q_head, Q, k, rows, scores, \
+                                       stream);                                                                                    \
+        if (dtype == kTableBF16)                                                                                                   \
+            return rescore_impl<M, DD>(static_cast<const __bf16*>(table), ld, row_base, q_fixed, q_rel, q_head, Q, k, rows, scores,   \
+                                       stream);                                                                                    \
+        return hipErrorInvalidValue;                                                                                               \
+    }
+#define BLP_RESCORE16_MODEL(M) BLP_RESCORE16_CASE(M, 64) BLP_RESCORE16_CASE(M, 128) BLP_RESCORE16_CASE(M, 256)
+    BLP_RESCORE16_MODEL(TRANSE) BLP_RESCORE16_MODEL(DISTMULT) BLP_RESCORE16_MODEL(COMPLEX) BLP_RESCORE16_MODEL(SIMPLE)
+#undef BLP_RESCORE16_MODEL
+#undef BLP_RESCORE16_CASE
+    return hipErrorInvalidValue;
+}
+
 template <int MODEL, int D, class T>
 static hipError_t topk_impl(const T* table, int64_t N, int64_t ld, int64_t row_base, const QRows& q_fixed, const QRows& q_rel,
                             int64_t q_head, int64_t q_tail, int k, const FilterSpec& filter, int64_t* rows, float* scores,

@@ -567,35 +567,40 @@ def rank_sets(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, tru
     return counts
 
 
-def topk_sets_supported(rel_model, dim, k):
-    """True if topk_sets takes this width and k (include/blp_hip.h: blp_topk_sets_supported -- the four models at 64 / 128 /
-    256, 1 <= k <= 256; a float32 table)."""
-    return bool(_lib.lib().blp_topk_sets_supported(_lib.MODEL_IDS[rel_model], int(dim), int(k)))
+def topk_sets_supported(rel_model, dim, k, dtype=torch.float32):
+    """True if topk_sets takes this width, k and table dtype (include/blp_hip.h: blp_topk_sets_typed_supported -- the four
+    models at 64 / 128 / 256, 1 <= k <= 256; a float32, float16 or bfloat16 table)."""
+    if dtype not in TABLE_DTYPES:
+        return False
+    return bool(_lib.lib().blp_topk_sets_typed_supported(_lib.MODEL_IDS[rel_model], TABLE_DTYPES[dtype], int(dim), int(k)))
 
 
 def topk_sets_workspace_bytes(rel_model, D, q_head, q_tail, num_sets, nnz, k):
     """Bytes of topk_sets' workspace: it depends on the queries, the number of sets, k and (boundedly) the number of set
-    entries -- never on the table's length."""
+    entries -- never on the table's length or its storage type."""
     return int(_lib.lib().blp_topk_sets_workspace_bytes(_lib.MODEL_IDS[rel_model], int(D), int(q_head), int(q_tail), int(num_sets),
                                                         int(nnz), int(k)))
 
 
 def topk_sets(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, set_ptr, set_rows, qset_ptr_head, qset_ptr_tail,
               filter=None, row_base=0, out=None):
-    """Filtered top-k prediction inside candidate sets that queries SHARE (blp_topk_sets).  Queries, sets and grouping as in
+    """Filtered top-k prediction inside candidate sets that queries SHARE (blp_topk_sets, blp_topk_sets_typed).  Queries, sets and grouping as in
     rank_sets -- head-replacing [0, q_head), then tail-replacing; fixed_row (Q,) indexes ``source`` (S, D) float32, rel_ids
     (Q,) index ``rel_emb`` (R, D); within each side GROUPED by set: set g serves head queries [qset_ptr_head[g],
     qset_ptr_head[g + 1]) and tail queries q_head + [qset_ptr_tail[g], qset_ptr_tail[g + 1]); set g is entries [set_ptr[g],
-    set_ptr[g + 1]) of ``set_rows`` (nnz,): GLOBAL rows of ``table`` (N, D) float32 -- which holds global rows [row_base,
+    set_ptr[g + 1]) of ``set_rows`` (nnz,): GLOBAL rows of ``table`` (N, D) (float32 / float16 / bfloat16; a 16-bit table needs
+    a float32 ``source``: the result is that of the table widened to float32) -- which holds global rows [row_base,
     row_base + N) --, strictly ascending within a set; entries outside the shard are skipped.  The output is topk's, taken over
     the query's set: the k entries with the highest score_fn value (descending score, ties by ascending row, NaN last), the
     rows ``filter`` (a SegmentFilter whose row_base is ``row_base``) names removed; slots beyond the entries left: row -1,
     score NaN.  Returns (rows (Q, k) int64, scores (Q, k) float32) in the caller's (grouped) order; ``out`` may give both."""
     _require_device(table, source, fixed_row, rel_emb, rel_ids, set_ptr, set_rows, qset_ptr_head, qset_ptr_tail)
-    if table.dtype != torch.float32:
-        raise TypeError(f"topk_sets reads a float32 table, got {table.dtype}")
+    if table.dtype not in TABLE_DTYPES:
+        raise TypeError(f"topk_sets reads a float32, float16 or bfloat16 table, got {table.dtype}")
+    if source.dtype != torch.float32:
+        raise TypeError(f"topk_sets needs a float32 `source` for the queries' vectors, got {source.dtype}")
     same = source is table
-    table = _f32_rows(table, "table")
+    table = _table_rows(table, "table")
     source = table if same else _f32_rows(source, "source")
     rel_emb = _f32_rows(rel_emb, "rel_emb").contiguous()
     N, D = table.shape
@@ -612,7 +617,7 @@ def topk_sets(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, 
         raise ValueError("set_ptr, qset_ptr_head and qset_ptr_tail need G + 1 entries each")
     if not 0 <= q_head <= Q:
         raise ValueError(f"q_head = {q_head} outside [0, {Q}]")
-    if not topk_sets_supported(rel_model, D, k):
+    if not topk_sets_supported(rel_model, D, k, table.dtype):
         raise ValueError(f"topk_sets: D = {D}, k = {k} not supported (D in 64 / 128 / 256, 1 <= k <= 256): see topk_sets_supported")
     if filter is not None and int(filter.row_base) != int(row_base):
         raise ValueError(f"topk_sets: the filter's row_base {filter.row_base} differs from row_base {row_base}")
@@ -628,16 +633,18 @@ def topk_sets(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, 
     L = _lib.lib()
     model = _lib.MODEL_IDS[rel_model]
     stream = torch._C._cuda_getCurrentRawStream(dev.index)
-    ws_bytes = L.blp_topk_sets_workspace_bytes(model, D, q_head, Q - q_head, G, nnz, k)
+    tdt = TABLE_DTYPES[table.dtype]
+    ws_bytes = L.blp_topk_sets_typed_workspace_bytes(model, tdt, D, q_head, Q - q_head, G, nnz, k)
     workspace = _workspace(dev, stream, ws_bytes)
     spec = None if filter is None else _filter_spec(filter, Q, dev)
-    status = L.blp_topk_sets(model, table.data_ptr(), N, D, table.stride(0) if N > 1 else D, int(row_base), source.data_ptr(),
-                             source.shape[0], source.stride(0) if source.shape[0] > 1 else D, fixed_row.data_ptr(), rel_emb.data_ptr(),
-                             rel_emb.shape[0], rel_ids.data_ptr(), q_head, Q - q_head, k, set_ptr.data_ptr(),
-                             _addr(set_rows) if nnz else None, nnz, G, qset_ptr_head.data_ptr(), qset_ptr_tail.data_ptr(), spec,
-                             rows.data_ptr(), scores.data_ptr(), workspace.data_ptr(), ws_bytes, dev.index, stream)
+    status = L.blp_topk_sets_typed(model, table.data_ptr(), tdt, N, D, table.stride(0) if tdt or N > 1 else D, int(row_base),
+                                   source.data_ptr(), source.shape[0], source.stride(0) if source.shape[0] > 1 else D,
+                                   fixed_row.data_ptr(), rel_emb.data_ptr(), rel_emb.shape[0], rel_ids.data_ptr(), q_head, Q - q_head, k,
+                                   set_ptr.data_ptr(), _addr(set_rows) if nnz else None, nnz, G, qset_ptr_head.data_ptr(),
+                                   qset_ptr_tail.data_ptr(), spec, rows.data_ptr(), scores.data_ptr(), workspace.data_ptr(), ws_bytes,
+                                   dev.index, stream)
     if status:
-        _lib.check(status, "blp_topk_sets")
+        _lib.check(status, "blp_topk_sets_typed" if tdt else "blp_topk_sets")
     return rows, scores
 
 

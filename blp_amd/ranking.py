@@ -1017,8 +1017,8 @@ def _topk_sets_dense(score_fn, table, fixed, rel, q_head, k, set_ptr, set_rows, 
                      max_bytes=1 << 28):
     """The dense route of predict_links_in_sets: score_fn of each set's gathered rows against its group's queries, in (query
     chunk, row slab) pieces of bounded bytes, the filter through _filtered_pairs, the order by _stable_topk.  Queries grouped by
-    set within each side, as blp_topk_sets takes them; fixed / rel (Q, D) float32.  CPU tensors and the widths and table dtypes
-    blp_topk_sets does not take; on CPU tensors it is the oracle of the fused route.  Returns (rows (Q, k) int64 global rows,
+    set within each side, as blp_topk_sets takes them; fixed / rel (Q, D) float32.  CPU tensors and the widths and k
+    blp_topk_sets / blp_topk_sets_typed do not take; on CPU tensors it is the oracle of the fused route.  Returns (rows (Q, k) int64 global rows,
     scores (Q, k) float32)."""
     Q, (N, D) = fixed.shape[0], table.shape
     dev = table.device
@@ -1071,9 +1071,10 @@ def predict_links_in_sets(model, table, triples, k, sets, ent2idx, *, set_ids=No
     entities     optional (num_entities,) entity id of every table row: ids instead of rows are returned
     Returns predict_links' result, (rows or ids (Q, k) int64, scores (Q, k) float32) in the caller's order: descending score,
     ties by ascending row, NaN last; -1 / NaN beyond the entries of the set that are left.  Scores are score_fn's values bit
-    for bit.  A float32 HIP table at 64 / 128 / 256 and k <= 256 goes through blp_topk_sets (a row of a set is fetched once per
-    chunk of its group's queries); CPU tensors, other widths and 16-bit tables take the dense route: score_fn on gathered
-    rows and a stable sort."""
+    for bit (of the table widened to float32).  A float32, float16 or bfloat16 HIP table at 64 / 128 / 256 and k <= 256 goes
+    through blp_topk_sets / blp_topk_sets_typed (a row of a set is fetched once per chunk of its group's queries; a 16-bit
+    table is read as it is, only the Q fixed rows are gathered and widened); CPU tensors, other widths and k > 256 take the
+    dense route: score_fn on gathered rows and a stable sort."""
     model = _module(model)
     if side not in ("head", "tail", "both"):
         raise ValueError(f"side must be 'head', 'tail' or 'both', got {side!r}")
@@ -1118,8 +1119,15 @@ def predict_links_in_sets(model, table, triples, k, sets, ent2idx, *, set_ids=No
         sel = torch.cat([x for x, on in ((torch.arange(T, device=device), heads), (torch.arange(T, 2 * T, device=device), tails)) if on])[perm]
         filt = ops.SegmentFilter(seg.seg_lo[sel].contiguous(), seg.seg_hi[sel].contiguous(), seg.values,
                                  seg.exclude[sel].contiguous(), seg.ent2idx, 0)
-    if table.is_cuda and table.dtype == torch.float32 and k <= 256 and ops.topk_sets_supported(model.rel_model, D, k):
-        g_rows, g_scores = ops.topk_sets(model.rel_model, table, table, g_fixed, rel_w, g_rel, q_head, k, set_ptr, set_rows,
+    if table.is_cuda and k <= 256 and ops.topk_sets_supported(model.rel_model, D, k, table.dtype):
+        if table.dtype != torch.float32:
+            # float32 query vectors: the Q fixed rows gathered and widened (exact) by the library's own kernel
+            # (blp_gather_triple_vectors: 64-bit offsets, a table of more than 2^31 bytes included)
+            pairs = torch.stack((g_fixed, g_fixed, torch.zeros_like(g_fixed)), dim=1)
+            source, src_fixed = ops.gather_triple_vectors(pairs, None, table)[:Q], torch.arange(Q, device=device)
+        else:
+            source, src_fixed = table, g_fixed
+        g_rows, g_scores = ops.topk_sets(model.rel_model, table, source, src_fixed, rel_w, g_rel, q_head, k, set_ptr, set_rows,
                                          qptr_head, qptr_tail, filter=filt)
     else:
         dense_filt = None if filt is None else (filt.seg_lo, filt.seg_hi, filt.values, filt.exclude, filt.ent2idx)

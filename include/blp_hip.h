@@ -639,6 +639,24 @@ int blp_topk_sets(int model, const float *table, int64_t N, int D, int64_t ld, i
                   int64_t q_tail, int k, const int64_t *set_ptr, const int64_t *set_row, int64_t nnz, int64_t G,
                   const int64_t *qset_ptr_head, const int64_t *qset_ptr_tail, const blp_filter *filter, int64_t *rows,
                   float *scores, void *workspace, size_t workspace_bytes, int device, void *stream);
+/* blp_topk_sets over a candidate table in any storage type (table_dtype: BLP_DTYPE_*; see "THE CANDIDATE TABLE MAY COME IN A
+ * 16-BIT STORAGE TYPE" above): the same contract on the table WIDENED to f32 exactly -- the same rows in the same order and
+ * the reference's f32 scores of the widened rows bit for bit (sign of zero included), with the same set, shard (row_base),
+ * filter / exclude semantics, the same -1 / quiet-NaN slots, the same limits and the same workspace (it does not depend on the
+ * storage type), independent of the grid.  A 16-bit table's row stride ld is in ELEMENTS, ld % 8 == 0, 16-byte aligned base;
+ * source and rel_emb stay f32 (the queries' vectors: gather and widen the Q fixed rows, blp_gather_triple_vectors).
+ * BLP_DTYPE_F32 is blp_topk_sets itself.  An unknown table_dtype is BLP_ERR_BAD_ARG (the _supported / _workspace_bytes calls
+ * answer 0).  The 16-bit rows are gathered as they are: half the cache lines of the f32 table per set entry.
+ * (Added after 6.0.0 without a version change: no existing entry point changed.) */
+int blp_topk_sets_typed_supported(int model, int table_dtype, int D, int k);
+size_t blp_topk_sets_typed_workspace_bytes(int model, int table_dtype, int D, int64_t q_head, int64_t q_tail, int64_t G,
+                                           int64_t nnz, int k);
+int blp_topk_sets_typed(int model, const void *table, int table_dtype, int64_t N, int D, int64_t ld, int64_t row_base,
+                        const float *source, int64_t S, int64_t ld_src, const int64_t *fixed_row, const float *rel_emb, int64_t R,
+                        const int64_t *rel_id, int64_t q_head, int64_t q_tail, int k, const int64_t *set_ptr,
+                        const int64_t *set_row, int64_t nnz, int64_t G, const int64_t *qset_ptr_head,
+                        const int64_t *qset_ptr_tail, const blp_filter *filter, int64_t *rows, float *scores, void *workspace,
+                        size_t workspace_bytes, int device, void *stream);
 
 /* --------------------------------------------------------------------------------------------
  * Re-ranking a first-stage retrieval run (reference retrieval.py rerank: BM25F candidates of DBpedia-Entity v2 re-scored

@@ -10,6 +10,16 @@ expanded route spent in blp_rank_lists, and the gather bandwidth of the new call
 topk_chunk(k) = 32 queries of its group, D x 4 bytes each).
 
     python tools/topk_sets_bench.py [--steps 30] [--warmup 3] [--only NAME ...] [--out profiles/topksets/topk_sets_bench.jsonl]
+                                    [--table16 {f16,bf16}] [--no-expanded] [--repeats 3]
+
+--table16: the table rounded to IEEE half / bfloat16 instead; blp_topk_sets_typed on the 16-bit table alternates with
+blp_topk_sets on that table widened to f32 (the yardstick), rows and scores required equal first; the alternation is repeated
+--repeats times, one JSON line with the median of every repeat for both calls, the f32 call's own spread over those medians,
+the ratio (16-bit over f32) and the gather bandwidth of both calls.  The expanded route is not run.
+--no-expanded: blp_topk_sets alone (the long table: the expanded route's flat sorts of 2 x 10^9 entries are not run), repeated
+--repeats times.
+--once NAME: one call of the workload after one of warm-up, nothing timed -- the program to put under a kernel trace for the
+split of the call by kernel (with --table16: the 16-bit call).
 
   fb15k237-{transe,distmult}   105 740 queries, 14 541 x 128 table, 474 sets of 50 .. 8 000 rows (log-uniform)
   longtable-transe             13 788 queries, 4.6 M x 128 table, 1 644 sets of 10^3 .. 10^6 rows (log-uniform)
@@ -50,7 +60,59 @@ def stable_topk_of_lists(scores, rows, removed, owner_local, ptr_local, n_querie
     return out_rows, out_scores
 
 
-def run(name, cfg, steps, warmup):
+def spread(medians):
+    """The spread of repeated medians, relative to their mean: (max - min) / mean."""
+    return round((max(medians) - min(medians)) / (sum(medians) / len(medians)), 4)
+
+
+def fetched_rows(set_ptr, qh, qt):
+    chunks = (torch.div(qh[1:] - qh[:-1] + QUERY_CHUNK - 1, QUERY_CHUNK, rounding_mode="floor") +
+              torch.div(qt[1:] - qt[:-1] + QUERY_CHUNK - 1, QUERY_CHUNK, rounding_mode="floor"))
+    return int(((set_ptr[1:] - set_ptr[:-1]) * chunks).sum())
+
+
+def run16(name, cfg, steps, warmup, table16, repeats, once, small, rel_w, fixed, rel_ids, q_head, set_ptr, set_row, qh, qt, filt, out):
+    """blp_topk_sets_typed on the 16-bit table next to blp_topk_sets on that table widened to f32."""
+    D, Q = cfg["D"], cfg["Q"]
+    wide = small.float()
+    out16 = (torch.empty_like(out[0]), torch.empty_like(out[1]))
+    # the queries' f32 vectors: the Q fixed rows widened (blp_gather_triple_vectors, as ranking.predict_links_in_sets gathers
+    # them) -- the same source for both calls
+    source = ops.gather_triple_vectors(torch.stack((fixed, fixed, torch.zeros_like(fixed)), dim=1), None, small)[:Q]
+    src_fixed = torch.arange(Q, device=wide.device)
+
+    def f32():
+        ops.topk_sets(cfg["model"], wide, source, src_fixed, rel_w, rel_ids, q_head, K, set_ptr, set_row, qh, qt, filter=filt, out=out)
+
+    def t16():
+        ops.topk_sets(cfg["model"], small, source, src_fixed, rel_w, rel_ids, q_head, K, set_ptr, set_row, qh, qt, filter=filt, out=out16)
+
+    f32()
+    t16()
+    torch.cuda.synchronize()
+    if once:
+        return None
+    nan = torch.isnan(out[1])
+    same = bool(torch.equal(out16[0], out[0])) and bool(torch.equal(torch.isnan(out16[1]), nan)) and \
+        bool(torch.equal(out16[1][~nan].view(torch.int32), out[1][~nan].view(torch.int32)))
+    if not same:
+        return {"workload": name, **cfg, "k": K, "table16": table16, "results_equal": False}
+    a, b = [], []
+    for _ in range(repeats):
+        ms = measure({"f32": f32, "table16": t16}, steps, warmup)
+        a.append(stats(ms["f32"])["median"])
+        b.append(stats(ms["table16"])["median"])
+    ma, mb = float(np.median(a)), float(np.median(b))
+    rows = fetched_rows(set_ptr, qh, qt)
+    return {"workload": name, **cfg, "k": K, "table16": table16, "set_entries": int(set_row.numel()),
+            "filter_entries_per_query": FILTER_PER_QUERY, "results_equal": same, "f32_ms_medians": a, "table16_ms_medians": b,
+            "f32_ms": round(ma, 4), "table16_ms": round(mb, 4), "f32_spread": spread(a), "table16_spread": spread(b),
+            "table16_over_f32": round(mb / ma, 3), "fetched_bytes_table16": rows * D * 2,
+            "gather_TBps_table16": round(rows * D * 2 / (mb * 1e-3) / 1e12, 3), "gather_TBps_f32": round(rows * D * 4 / (ma * 1e-3) / 1e12, 3),
+            "steps": steps, "repeats": repeats}
+
+
+def run(name, cfg, steps, warmup, table16=None, expanded_route=True, repeats=3, once=False):
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(0)
     rng = np.random.default_rng(0)
@@ -86,8 +148,30 @@ def run(name, cfg, steps, warmup):
     filt = ops.SegmentFilter(lo, lo + FILTER_PER_QUERY, seg.reshape(-1).contiguous(), None, None, 0)
     out = (torch.empty((Q, K), dtype=torch.int64, device=dev), torch.empty((Q, K), dtype=torch.float32, device=dev))
 
+    if table16:  # (the f32 original is not kept: the 16-bit copy and its widened image replace it)
+        small = table.to({"f16": torch.float16, "bf16": torch.bfloat16}[table16])
+        del table
+        return run16(name, cfg, steps, warmup, table16, repeats, once, small, rel_w, fixed, rel_ids, q_head, set_ptr, set_row, qh, qt, filt, out)
+
     def fused():
         ops.topk_sets(cfg["model"], table, table, fixed, rel_w, rel_ids, q_head, K, set_ptr, set_row, qh, qt, filter=filt, out=out)
+
+    if once:
+        fused()
+        fused()
+        torch.cuda.synchronize()
+        return None
+    if not expanded_route:
+        fused()
+        medians = [stats(measure({"topk_sets": fused}, steps, warmup)["topk_sets"])["median"] for _ in range(repeats)]
+        m = float(np.median(medians))
+        rows, pairs = fetched_rows(set_ptr, qh, qt), int(n_per.sum())
+        return {"workload": name, **cfg, "k": K, "set_entries": int(set_row.numel()), "pairs": pairs,
+                "filter_entries_per_query": FILTER_PER_QUERY, "topk_sets_ms_medians": medians, "topk_sets_ms": round(m, 4),
+                "topk_sets_spread": spread(medians), "fetched_bytes": rows * D * 4, "gather_TBps": round(rows * D * 4 / (m * 1e-3) / 1e12, 3),
+                "pairs_per_s": round(pairs / (m * 1e-3), 0), "valid_slots": int((out[0] >= 0).sum()),
+                "workspace_bytes": ops.topk_sets_workspace_bytes(cfg["model"], D, q_head, Q - q_head, G, int(set_row.numel()), K),
+                "steps": steps, "repeats": repeats}
 
     # the expanded route: per-query lists in calls of at most MAX_LIST_ENTRIES entries, each of one side; what the filter
     # removes is marked per entry once, outside the timing (blp_rank_lists' scores are unfiltered)
@@ -132,9 +216,7 @@ def run(name, cfg, steps, warmup):
         return {"workload": name, **cfg, "k": K, "results_equal": False}
     ms = measure({"topk_sets": fused, "expanded_lists_topk": expanded, "expanded_lists_scores_only": expanded_scores}, steps, warmup)
     s, e, sc = stats(ms["topk_sets"]), stats(ms["expanded_lists_topk"]), stats(ms["expanded_lists_scores_only"])
-    chunks = (torch.div(qh[1:] - qh[:-1] + QUERY_CHUNK - 1, QUERY_CHUNK, rounding_mode="floor") +
-              torch.div(qt[1:] - qt[:-1] + QUERY_CHUNK - 1, QUERY_CHUNK, rounding_mode="floor"))
-    fetched = int(((set_ptr[1:] - set_ptr[:-1]) * chunks).sum()) * D * 4
+    fetched = fetched_rows(set_ptr, qh, qt) * D * 4
     pairs = int(n_per.sum())
     return {"workload": name, **cfg, "k": K, "set_entries": int(set_row.numel()), "pairs": pairs, "expanded_calls": len(calls),
             "expanded_index_bytes": pairs * 8, "filter_entries_per_query": FILTER_PER_QUERY, "results_equal": same,
@@ -151,11 +233,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--only", nargs="*")
     ap.add_argument("--out", default=DEFAULT_OUT)
+    ap.add_argument("--table16", choices=("f16", "bf16"))
+    ap.add_argument("--no-expanded", action="store_true")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--once", metavar="NAME")
     args = ap.parse_args()
+    if args.once:
+        run(args.once, WORKLOADS[args.once], 0, 0, args.table16, once=True)
+        return
     for name, cfg in WORKLOADS.items():
         if args.only and name not in args.only:
             continue
-        line = json.dumps(run(name, cfg, args.steps, args.warmup))
+        line = json.dumps(run(name, cfg, args.steps, args.warmup, args.table16, not args.no_expanded, args.repeats))
         print(line, flush=True)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
