@@ -824,6 +824,74 @@ int blp_rank_lists(int model, const void* table, int table_dtype, int64_t N, int
     return BLP_OK;
 }
 
+// ---- filtered top-k inside per-query candidate lists (lists_topk.hip)
+int blp_topk_lists_supported(int model, int table_dtype, int D, int k) {
+    return valid_model(model) && blp::topk_lists_supported(model, table_dtype, D, k) ? 1 : 0;
+}
+
+size_t blp_topk_lists_workspace_bytes(int model, int table_dtype, int D, int64_t q_head, int64_t q_tail, int64_t nnz, int k) {
+    if (!blp_topk_lists_supported(model, table_dtype, D, k) || q_head < 0 || q_tail < 0 || nnz < 0 || nnz >= (1ll << 31) ||
+        q_head + q_tail > (1ll << 30) || q_head + q_tail >= ((1ll << 31) + k - 1) / k)
+        return 0;
+    return blp::topk_lists_workspace_bytes(q_head, q_tail, nnz, k);
+}
+
+// (blp_rank_lists' checks of the queries, the table and the lists, restated under this entry's name rather than shared: there
+// they are interleaved with the checks of counts / true_row / scores, and their order and messages are pinned by its tests)
+int blp_topk_lists(int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld, int64_t row_base, const float* source,
+                   int64_t S, int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R, const int64_t* rel_id,
+                   int64_t q_head, int64_t q_tail, const int64_t* list_ptr, const int64_t* list_row, int64_t nnz, int k,
+                   const blp_filter* filter, int64_t* rows, float* scores, void* workspace, size_t workspace_bytes, int device,
+                   void* stream) {
+    const char* who = "blp_topk_lists";
+    if (!valid_model(model)) return fail(BLP_ERR_BAD_ARG, "%s: unknown model %d", who, model);
+    if (!valid_table_dtype(table_dtype)) return fail(BLP_ERR_BAD_ARG, "%s: unknown table dtype %d", who, table_dtype);
+    if (k < 1 || k > 256) return fail(BLP_ERR_BAD_ARG, "%s: k = %d outside [1, 256]", who, k);
+    if (!blp_topk_lists_supported(model, table_dtype, D, k))
+        return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (TransE: D %% 4 == 0 up to 1024; the other models: 64 / 128 / "
+                                             "256: see blp_topk_lists_supported)", who, D);
+    if (N < 0 || q_head < 0 || q_tail < 0 || ld < D || row_base < 0 || nnz < 0)
+        return fail(BLP_ERR_BAD_ARG, "%s: negative size / row_base or ld < D (N=%lld q_head=%lld q_tail=%lld ld=%lld nnz=%lld)", who,
+                    (long long)N, (long long)q_head, (long long)q_tail, (long long)ld, (long long)nnz);
+    if (nnz >= (1ll << 31)) return fail(BLP_ERR_BAD_ARG, "%s: nnz = %lld list entries, at most 2^31 - 1", who, (long long)nnz);
+    const int64_t Q = q_head + q_tail;
+    if (row_base + N > (1ll << 31) || Q > (1ll << 30) || Q >= ((1ll << 31) + k - 1) / k)
+        return fail(BLP_ERR_BAD_ARG, "%s: global rows must stay below 2^31, Q below 2^30 and Q x k below 2^31", who);
+    if (!rows || !scores) return fail(BLP_ERR_BAD_ARG, "%s: NULL rows / scores", who);
+    if (Q > 0 && (!source || !fixed_row || !rel_id || !rel_emb || !list_ptr || R <= 0 || S <= 0))
+        return fail(BLP_ERR_BAD_ARG, "%s: NULL source / fixed_row / rel_id / rel_emb / list_ptr, or R <= 0 / S <= 0", who);
+    if (nnz > 0 && (Q == 0 || !list_row)) return fail(BLP_ERR_BAD_ARG, "%s: %lld list entries but no query, or NULL list_row", who, (long long)nnz);
+    if (N > 0 && !table) return fail(BLP_ERR_BAD_ARG, "%s: NULL table", who);
+    if (!table_rows_aligned(table, table_dtype, ld) || !aligned16(source) || (ld_src & 3) || ld_src < D || !aligned16(rel_emb))
+        return fail(BLP_ERR_BAD_ARG, table_dtype == BLP_DTYPE_F32
+                                         ? "%s: table / source / rel_emb must be 16-byte aligned, ld %% 4 == 0, ld_src %% 4 == 0, ld_src >= D"
+                                         : "%s: table / source / rel_emb must be 16-byte aligned, ld %% 8 == 0 (a 16-bit table's row stride, "
+                                           "in elements), ld_src %% 4 == 0, ld_src >= D",
+                    who);
+    blp::FilterSpec spec;
+    if (filter) {
+        if (!filter->seg_lo || !filter->seg_hi || !filter->values || (filter->ent2idx && filter->ent2idx_len < 0))
+            return fail(BLP_ERR_BAD_ARG, "%s: filter needs seg_lo, seg_hi and values (ent2idx_len >= 0)", who);
+        if (filter->row_base != row_base)
+            return fail(BLP_ERR_BAD_ARG, "%s: filter row_base %lld differs from the call's row_base %lld", who,
+                        (long long)filter->row_base, (long long)row_base);
+        spec.lo = filter->seg_lo; spec.hi = filter->seg_hi; spec.val = filter->values; spec.exclude = filter->exclude;
+        spec.ent2idx = filter->ent2idx; spec.ent2idx_len = filter->ent2idx ? filter->ent2idx_len : 0;
+        spec.row_base = filter->row_base;
+    }
+    if (Q == 0) return BLP_OK;
+    const size_t need = blp::topk_lists_workspace_bytes(q_head, q_tail, nnz, k);
+    if (need && (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255u)))
+        return fail(BLP_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned and >= %zu bytes (got %zu)", who, need, workspace_bytes);
+    DeviceGuard guard(device);
+    if (guard.error() != hipSuccess) return hip_fail(guard.error(), "hipSetDevice");
+    hipError_t err = blp::launch_topk_lists(model, D, table_dtype, table, N, ld, row_base, blp::QRows::rows_of(source, fixed_row, ld_src),
+                                            blp::QRows::rows_of(rel_emb, rel_id, D), q_head, q_tail, list_ptr, list_row, nnz, k, spec,
+                                            rows, scores, workspace, static_cast<hipStream_t>(stream));
+    if (err != hipSuccess) return hip_fail(err, "blp_topk_lists launch");
+    return BLP_OK;
+}
+
 // ---- candidate sets shared between queries (rank_sets.hip)
 int blp_rank_sets_supported(int model, int D) { return valid_model(model) && blp::rank_sets_supported(model, D) ? 1 : 0; }
 

@@ -119,6 +119,16 @@ hipError_t launch_rank_lists(int model, int D, int dtype, const void* table, int
                              const int64_t* list_ptr, const int64_t* list_row, int64_t nnz, const FilterSpec& filter, int32_t* counts,
                              float* scores, void* workspace, hipStream_t stream);
 
+// lists_topk.hip: filtered top-k inside per-query candidate lists (include/blp_hip.h: blp_topk_lists): rank_lists' queries,
+// table and lists, topk's output.  The workspace holds the (Q, S, k) partial key lists when a query's list is cut into S > 1
+// slabs (S from Q and nnz alone), else nothing.
+bool topk_lists_supported(int model, int dtype, int D, int k);
+size_t topk_lists_workspace_bytes(int64_t q_head, int64_t q_tail, int64_t nnz, int k);
+hipError_t launch_topk_lists(int model, int D, int dtype, const void* table, int64_t N, int64_t ld, int64_t row_base,
+                             const QRows q_fixed, const QRows q_rel, int64_t q_head, int64_t q_tail, const int64_t* list_ptr,
+                             const int64_t* list_row, int64_t nnz, int k, const FilterSpec& filter, int64_t* rows, float* scores,
+                             void* workspace, hipStream_t stream);
+
 // rerank.hip: re-ranking a retrieval run (include/blp_hip.h: blp_rerank_cosine, blp_rerank_ndcg)
 constexpr int kRerankMaxSegment = 8192;  // candidates per query: 8 192 keys of 8 bytes = 64 KiB of LDS
 constexpr int kRerankMaxCutoffs = 8;

@@ -648,6 +648,84 @@ def topk_sets(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, 
     return rows, scores
 
 
+def topk_lists_supported(rel_model, dim, k, dtype=torch.float32):
+    """True if topk_lists takes this width, k and table dtype (include/blp_hip.h: blp_topk_lists_supported -- rank_lists'
+    widths: TransE at any D % 4 == 0 up to 1024, the other models at 64 / 128 / 256; 1 <= k <= 256; a float32, float16 or
+    bfloat16 table)."""
+    if dtype not in TABLE_DTYPES:
+        return False
+    return bool(_lib.lib().blp_topk_lists_supported(_lib.MODEL_IDS[rel_model], TABLE_DTYPES[dtype], int(dim), int(k)))
+
+
+def topk_lists_workspace_bytes(rel_model, D, q_head, q_tail, nnz, k, dtype=torch.float32):
+    """Bytes of topk_lists' workspace: 0 while every list is one slab (2 048 queries or more, or short lists), else the
+    (Q, S, k) partial key lists -- never a function of the table's length or storage type."""
+    if dtype not in TABLE_DTYPES:
+        return 0
+    return int(_lib.lib().blp_topk_lists_workspace_bytes(_lib.MODEL_IDS[rel_model], TABLE_DTYPES[dtype], int(D), int(q_head),
+                                                         int(q_tail), int(nnz), int(k)))
+
+
+def topk_lists(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, list_ptr, list_row, k, filter=None, row_base=0,
+               out=None):
+    """Filtered top-k prediction inside per-query candidate lists (blp_topk_lists).  Queries, table and lists as in rank_lists
+    -- head-replacing [0, q_head), then tail-replacing; fixed_row (Q,) indexes ``source`` (S, D) float32, rel_ids (Q,) index
+    ``rel_emb`` (R, D); query q owns entries [list_ptr[q], list_ptr[q + 1]) of ``list_row`` (nnz,) int64 GLOBAL rows of
+    ``table`` (N, D) (float32 / float16 / bfloat16; a 16-bit table needs a float32 ``source``: the result is that of the table
+    widened to float32), which holds global rows [row_base, row_base + N); entries outside are skipped.  The output is topk's,
+    taken over the query's list: the k entries with the highest score_fn value (descending score, ties by ascending row, NaN
+    last), the rows ``filter`` (a SegmentFilter whose row_base is ``row_base``) names removed; a list is a multiset: a row
+    listed twice may come back twice; slots beyond the entries left: row -1, score NaN.
+    Returns (rows (Q, k) int64, scores (Q, k) float32); ``out`` may give both."""
+    _require_device(table, source, fixed_row, rel_emb, rel_ids, list_ptr, list_row)
+    if table.dtype not in TABLE_DTYPES:
+        raise TypeError(f"topk_lists reads a float32, float16 or bfloat16 table, got {table.dtype}")
+    if source.dtype != torch.float32:
+        raise TypeError(f"topk_lists needs a float32 `source` for the queries' vectors, got {source.dtype}")
+    same = source is table
+    table = _table_rows(table, "table")
+    source = table if same else _f32_rows(source, "source")
+    rel_emb = _f32_rows(rel_emb, "rel_emb").contiguous()
+    N, D = table.shape
+    if source.dim() != 2 or source.shape[1] != D:
+        raise ValueError(f"source must be (S, {D}), got {tuple(source.shape)}")
+    fixed_row, rel_ids, list_ptr, list_row = _i64_vector(fixed_row), _i64_vector(rel_ids), _i64_vector(list_ptr), _i64_vector(list_row)
+    Q, nnz = fixed_row.shape[0], list_row.shape[0]
+    k = int(k)
+    if rel_ids.shape[0] != Q or list_ptr.shape[0] != Q + 1 or rel_emb.dim() != 2 or rel_emb.shape[1] != D:
+        raise ValueError("fixed_row and rel_ids need one entry per query, list_ptr Q + 1; rel_emb must be (R, D)")
+    if not 0 <= q_head <= Q:
+        raise ValueError(f"q_head = {q_head} outside [0, {Q}]")
+    if not topk_lists_supported(rel_model, D, k, table.dtype):
+        raise ValueError(f"topk_lists: D = {D}, k = {k} not supported for {rel_model} (1 <= k <= 256: see topk_lists_supported)")
+    if filter is not None and int(filter.row_base) != int(row_base):
+        raise ValueError(f"topk_lists: the filter's row_base {filter.row_base} differs from row_base {row_base}")
+    dev = table.device
+    if out is None:
+        out = (torch.empty((Q, k), dtype=torch.int64, device=dev), torch.empty((Q, k), dtype=torch.float32, device=dev))
+    rows, scores = out
+    if rows.shape != (Q, k) or rows.dtype != torch.int64 or not rows.is_contiguous() or scores.shape != (Q, k) or \
+            scores.dtype != torch.float32 or not scores.is_contiguous():
+        raise ValueError("out must be contiguous (Q, k) int64 rows and (Q, k) float32 scores")
+    if Q == 0:
+        return rows, scores
+    L = _lib.lib()
+    model = _lib.MODEL_IDS[rel_model]
+    tdt = TABLE_DTYPES[table.dtype]
+    stream = torch._C._cuda_getCurrentRawStream(dev.index)
+    ws_bytes = L.blp_topk_lists_workspace_bytes(model, tdt, D, q_head, Q - q_head, nnz, k)
+    workspace = _workspace(dev, stream, ws_bytes) if ws_bytes else None
+    spec = None if filter is None else _filter_spec(filter, Q, dev)
+    status = L.blp_topk_lists(model, table.data_ptr(), tdt, N, D, table.stride(0) if tdt or N > 1 else D, int(row_base),
+                              source.data_ptr(), source.shape[0], source.stride(0) if source.shape[0] > 1 else D, fixed_row.data_ptr(),
+                              rel_emb.data_ptr(), rel_emb.shape[0], rel_ids.data_ptr(), q_head, Q - q_head, list_ptr.data_ptr(),
+                              _addr(list_row) if nnz else None, nnz, k, spec, rows.data_ptr(), scores.data_ptr(), _addr(workspace),
+                              ws_bytes, dev.index, stream)
+    if status:
+        _lib.check(status, "blp_topk_lists")
+    return rows, scores
+
+
 def topk_merge(rows, scores, k):
     """The k best of per-query candidate lists (blp_topk_merge): rows (Q, n) int64 global rows (< 0: an empty slot) and
     scores (Q, n) float32 -- e.g. the topk results of several candidate shards side by side -- in topk's order.

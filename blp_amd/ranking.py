@@ -766,6 +766,147 @@ def rank_candidates(model, table, triples, candidates, ent2idx, *, side="both", 
     return counts, (scores if rect is None else scores.reshape(rect.shape))
 
 
+def _topk_lists_dense(score_fn, table, fixed, rel, q_head, k, ptr, rows, row_base, filt, max_bytes=1 << 28):
+    """The dense route of predict_from_candidates: score_fn on the gathered rows of the lists, in query chunks of bounded
+    bytes, the filter through _filtered_pairs, the order by _stable_topk on the chunk's lists padded to a rectangle.  CPU
+    tensors, and the widths and k blp_topk_lists does not take; on CPU tensors it is the oracle of the fused route.
+    fixed / rel: (Q, D) float32; ptr (Q + 1,), rows (nnz,) global rows (a multiset; entries outside [row_base, row_base + N)
+    are skipped).  Returns (rows (Q, k) int64 global rows, scores (Q, k) float32)."""
+    Q, (N, D) = fixed.shape[0], table.shape
+    dev = table.device
+    rows_out = torch.full((Q, k), -1, dtype=torch.int64, device=dev)
+    scores_out = torch.full((Q, k), float("nan"), dtype=torch.float32, device=dev)
+    budget = max(1, max_bytes // (12 * D))  # slots of the chunk's rectangle: three gathered (n, D) float32 operands at most
+    ptr_host = ptr.tolist()
+    lo = 0
+    while lo < Q:
+        hi, width = lo + 1, ptr_host[lo + 1] - ptr_host[lo]
+        while hi < Q and (hi + 1 - lo) * max(width, ptr_host[hi + 1] - ptr_host[hi]) <= budget:
+            width = max(width, ptr_host[hi + 1] - ptr_host[hi])
+            hi += 1
+        p0, p1 = ptr_host[lo], ptr_host[hi]
+        if p1 > p0:
+            n_per = ptr[lo + 1:hi + 1] - ptr[lo:hi]
+            owner = torch.repeat_interleave(torch.arange(hi - lo, device=dev), n_per, output_size=p1 - p0)
+            local = rows[p0:p1] - row_base
+            valid = (local >= 0) & (local < N)
+            safe = torch.where(valid, local, torch.zeros_like(local))
+            e = table[safe].float() if N else table.new_zeros((p1 - p0, D)).float()
+            f, r = fixed[lo:hi][owner], rel[lo:hi][owner]
+            is_head = owner < q_head - lo
+            s = torch.empty((p1 - p0,), dtype=torch.float32, device=dev)
+            if bool(is_head.any()):
+                s[is_head] = score_fn(e[is_head], f[is_head], r[is_head])
+            if bool((~is_head).any()):
+                s[~is_head] = score_fn(f[~is_head], e[~is_head], r[~is_head])
+            f_owner, f_local = _filtered_pairs(filt, lo, hi, row_base, N, dev)
+            span = max(N, 1)
+            gone = torch.isin(owner * span + safe, f_owner * span + f_local)
+            col = torch.arange(p1 - p0, device=dev) - (ptr[lo:hi] - p0)[owner]
+            shape = (hi - lo, width)
+            r_rect = torch.full(shape, -1, dtype=torch.int64, device=dev)
+            s_rect = torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
+            g_rect = torch.zeros(shape, dtype=torch.bool, device=dev)
+            r_rect[owner, col] = torch.where(valid, local + row_base, torch.full_like(local, -1))
+            s_rect[owner, col] = s
+            g_rect[owner, col] = gone
+            rows_out[lo:hi], scores_out[lo:hi] = _stable_topk(s_rect, r_rect, g_rect, k)
+        lo = hi
+    return rows_out, scores_out
+
+
+def predict_from_candidates(model, table, triples, k, candidates, ent2idx, *, side="both", filter_index=None,
+                            candidates_are="rows", entities=None, unique=False):
+    """predict_links over a candidate list of each query's own -- what a first stage (BM25, a type index, an ANN probe) hands
+    over for re-ranking: for every triple (head, tail, rel) of ``triples`` (T, 3) the k entries of the query's list the model
+    scores highest as the replaced entity, known edges removed.  Only the listed rows are read.
+    triples      ``side`` "head": (?, r, t); "tail": (h, r, ?); "both": Q = 2 T queries in predict_links' order [heads | tails]
+    candidates   (Q, C) int64, padded with -1, or a CSR pair (ptr (Q + 1,), rows (nnz,)); table rows, or entity ids mapped
+                 through ``ent2idx`` with candidates_are="ids" (an id without a row is skipped) -- rank_candidates' forms.  A
+                 list is a multiset: a row listed twice may come back twice (adjacent, same score) unless ``unique``
+    ent2idx      utils.make_ent2idx map (entity id -> table row); the fixed entity of every query must have a row
+    filter_index utils.FilterIndex of the known edges: the rows it names are removed, every copy, not demoted (the entity at
+                 the replaced position is never removed: pass -1 there to have every known edge filtered)
+    entities     optional (num_entities,) entity id of every table row: ids instead of rows are returned
+    unique       True: duplicate rows within a list are dropped (torch ops) before the call
+    Returns predict_links' result, (rows or ids (Q, k) int64, scores (Q, k) float32): descending score, ties by ascending row,
+    NaN last; -1 / NaN beyond the entries of the list that are left.  Scores are score_fn's values bit for bit (of the table
+    widened to float32).  A float32, float16 or bfloat16 HIP table at a width blp_topk_lists takes and k <= 256 goes through
+    it (a 16-bit table is read as it is, only the Q fixed rows are gathered and widened); CPU tensors, other widths and
+    k > 256 take the dense route: score_fn on gathered rows and a stable sort."""
+    model = _module(model)
+    if side not in ("head", "tail", "both"):
+        raise ValueError(f"side must be 'head', 'tail' or 'both', got {side!r}")
+    if candidates_are not in ("rows", "ids"):
+        raise ValueError(f"candidates_are must be 'rows' or 'ids', got {candidates_are!r}")
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"k = {k} must be >= 1")
+    device = table.device
+    N, D = table.shape
+    triples = triples.to(device=device, dtype=torch.long).reshape(-1, 3)
+    ent2idx = ent2idx.to(device=device, dtype=torch.long)
+    T = triples.shape[0]
+    h, t, r = triples[:, 0], triples[:, 1], triples[:, 2]
+    heads, tails = side in ("head", "both"), side in ("tail", "both")
+    q_head = T if heads else 0
+    fixed_ids = torch.cat([x for x, on in ((t, heads), (h, tails)) if on])
+    rel_ids = torch.cat([r] * (int(heads) + int(tails)))
+    Q = fixed_ids.shape[0]
+
+    def to_rows(ids):
+        known = (ids >= 0) & (ids < ent2idx.shape[0])
+        return torch.where(known, ent2idx[torch.where(known, ids, torch.zeros_like(ids))], torch.full_like(ids, -1))
+
+    fixed_rows = to_rows(fixed_ids)
+    rel_w = model.rel_emb.weight.detach()
+    if Q and bool(((fixed_rows < 0) | (fixed_rows >= N) | (rel_ids < 0) | (rel_ids >= rel_w.shape[0])).any()):
+        raise ValueError("predict_from_candidates: a query's fixed entity has no table row, or its relation is out of range")
+    if isinstance(candidates, (tuple, list)):
+        ptr, rows = (x.to(device=device, dtype=torch.long).reshape(-1) for x in candidates)
+        if ptr.shape[0] != Q + 1:
+            raise ValueError(f"candidates: ptr must have Q + 1 = {Q + 1} entries, got {ptr.shape[0]}")
+    else:
+        rect = candidates.to(device=device, dtype=torch.long)
+        if rect.dim() != 2 or rect.shape[0] != Q:
+            raise ValueError(f"candidates must be (Q, C) with Q = {Q}, got {tuple(rect.shape)}")
+        ptr = torch.arange(Q + 1, device=device, dtype=torch.long) * rect.shape[1]
+        rows = rect.reshape(-1)
+    if candidates_are == "ids":
+        rows = to_rows(rows)
+    if Q == 0:
+        return torch.empty((0, k), dtype=torch.int64, device=device), torch.empty((0, k), dtype=torch.float32, device=device)
+    if unique and rows.numel():
+        # one entry per (query, row): the pairs as single integers, sorted and de-duplicated; entries without a row of the
+        # table would be skipped anyway and are dropped here
+        owner = torch.repeat_interleave(torch.arange(Q, device=device), ptr[1:] - ptr[:-1], output_size=rows.shape[0])
+        ok = (rows >= 0) & (rows < N)
+        pairs = torch.unique(owner[ok] * max(N, 1) + rows[ok])
+        rows = pairs % max(N, 1)
+        ptr = torch.cat((ptr.new_zeros(1), torch.cumsum(torch.bincount(pairs // max(N, 1), minlength=Q), 0)))
+    filt = None
+    if filter_index is not None:
+        seg = filter_index.segments(triples, ent2idx, device)
+        sel = torch.cat([x for x, on in ((torch.arange(T, device=device), heads), (torch.arange(T, 2 * T, device=device), tails)) if on])
+        filt = ops.SegmentFilter(seg.seg_lo[sel].contiguous(), seg.seg_hi[sel].contiguous(), seg.values,
+                                 seg.exclude[sel].contiguous(), seg.ent2idx, 0)
+    if table.is_cuda and k <= 256 and ops.topk_lists_supported(model.rel_model, D, k, table.dtype):
+        if table.dtype != torch.float32:  # float32 query vectors: the Q fixed rows, gathered and widened (exact)
+            source, src_fixed = table[fixed_rows].float(), torch.arange(Q, device=device)
+        else:
+            source, src_fixed = table, fixed_rows
+        out_rows, scores = ops.topk_lists(model.rel_model, table, source, src_fixed, rel_w, rel_ids, q_head, ptr, rows, k,
+                                          filter=filt)
+    else:
+        dense_filt = None if filt is None else (filt.seg_lo, filt.seg_hi, filt.values, filt.exclude, filt.ent2idx)
+        out_rows, scores = _topk_lists_dense(model.score_fn, table, table[fixed_rows].float(), rel_w[rel_ids], q_head, k, ptr,
+                                             rows, 0, dense_filt)
+    if entities is not None:
+        entities = entities.to(device=device, dtype=torch.long)
+        out_rows = torch.where(out_rows >= 0, entities[out_rows.clamp(min=0)], out_rows)
+    return out_rows, scores
+
+
 # ----------------------------------------------------------------------------------- candidate sets shared between queries
 def _sets_from_pairs(owner, rows, num_sets):
     """(ptr (G + 1,), rows (nnz,)) of the sets {rows[i] : owner[i] == g}: each set sorted ascending, duplicates dropped."""

@@ -659,6 +659,50 @@ int blp_topk_sets_typed(int model, const void *table, int table_dtype, int64_t N
                         size_t workspace_bytes, int device, void *stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Filtered top-k INSIDE per-query candidate lists: ANSWER a query (h, r, ?) / (?, r, t) with the k entries of ITS OWN LIST
+ * the model scores highest -- the candidates a first stage (BM25, a type index, an ANN probe) hands over, re-ranked, known
+ * edges removed.  The contract is the union of blp_rank_lists' (queries, table, lists) and blp_topk's (output).  Only the
+ * listed rows are read; no score is written out and nothing is sorted.
+ *
+ * Queries, table and lists exactly as in blp_rank_lists (there is no true_row): Q = q_head + q_tail, head-replacing first;
+ * fixed_row indexes source (S, D) f32 (row stride ld_src), rel_id indexes rel_emb (R, D) contiguous; table (N, D) in
+ * table_dtype (BLP_DTYPE_*, widened exactly), row stride ld in elements -- GLOBAL rows [row_base, row_base + N); query q owns
+ * entries [list_ptr[q], list_ptr[q + 1]) of list_row (nnz) int64 GLOBAL rows, list_ptr (Q + 1) int64 trusted to be
+ * non-decreasing from 0 to nnz.  An entry outside [row_base, row_base + N) (-1 padding, another shard's row) is SKIPPED.
+ * A list is a MULTISET: every valid entry competes, so a row listed twice may come back twice -- in adjacent slots, with the
+ * same row and the same score.
+ * Output per query, k slots: rows (Q, k) int64 global rows, scores (Q, k) f32:
+ *   scores are score_fn's values bit for bit (the torch-CPU order of oracle/blp_oracle.c, sign of zero included; for a 16-bit
+ *          table: of the table widened to f32);
+ *   order: descending score by IEEE comparison, equal scores (-0 == +0) by ascending row, entries whose score is NaN after
+ *          every number (by row); a NaN score comes out as the quiet NaN 0x7fc00000, its row >= 0;
+ *   filter (optional): a blp_filter with blp_rank_lists' semantics whose row_base MUST equal this call's (else
+ *          BLP_ERR_BAD_ARG); filtered rows are REMOVED, a filter entry removes every copy of its row; exclude[q] is never
+ *          removed;
+ *   slots left over (an empty list, a list with fewer than k valid entries, a filter that leaves fewer): row -1, score
+ *          0x7fc00000.
+ * Shards: the per-shard results of several row_base shards, side by side, merged by blp_topk_merge equal the unsharded call.
+ * Limits: blp_topk_lists_supported(model, table_dtype, D, k) = blp_rank_lists_supported(model, table_dtype, D) and
+ * 1 <= k <= 256; nnz < 2^31; row_base + N <= 2^31; Q <= 2^30; Q x k < 2^31; table rows / source / rel_emb 16-byte aligned
+ * (ld % 4 == 0, a 16-bit table: ld % 8 == 0, in elements; ld_src % 4 == 0).  An unknown table_dtype is BLP_ERR_BAD_ARG (the
+ * _supported / _workspace_bytes calls answer 0).  Every check runs before a device is touched.
+ * Workspace: blp_topk_lists_workspace_bytes(...) bytes, 256-B aligned.  A query's list is cut into S slabs, S computed from Q
+ * and nnz alone: S = 1 when Q >= 2048, else min(ceil(2048 / Q), max(1, ceil(ceil(nnz / (64 Q)) / 4)), 256).  S = 1 needs no
+ * workspace (0 bytes, workspace may be NULL); S > 1 needs Q x S x k 8-byte keys rounded up to 256 bytes -- fewer than 4 096 lists
+ * of k keys whatever nnz, independent of N and the storage type.
+ * Asynchronous on `stream`, no host synchronisation, no allocation.  Deterministic: a query's result is the multiset of its k
+ * largest keys, so nothing depends on the grid or the slabs.
+ * (Added after 6.0.0 without a version change: no existing entry point changed.)
+ * -------------------------------------------------------------------------------------------- */
+int blp_topk_lists_supported(int model, int table_dtype, int D, int k);
+size_t blp_topk_lists_workspace_bytes(int model, int table_dtype, int D, int64_t q_head, int64_t q_tail, int64_t nnz, int k);
+int blp_topk_lists(int model, const void *table, int table_dtype, int64_t N, int D, int64_t ld, int64_t row_base,
+                   const float *source, int64_t S, int64_t ld_src, const int64_t *fixed_row, const float *rel_emb, int64_t R,
+                   const int64_t *rel_id, int64_t q_head, int64_t q_tail, const int64_t *list_ptr, const int64_t *list_row,
+                   int64_t nnz, int k, const blp_filter *filter, int64_t *rows, float *scores, void *workspace,
+                   size_t workspace_bytes, int device, void *stream);
+
+/* --------------------------------------------------------------------------------------------
  * Re-ranking a first-stage retrieval run (reference retrieval.py rerank: BM25F candidates of DBpedia-Entity v2 re-scored
  * with entity embeddings, the mixing weight alpha chosen per fold by nDCG@100).  Candidates are a CSR over Q queries:
  * query q owns candidates [cand_ptr[q], cand_ptr[q + 1]) (cand_ptr (Q + 1) int64, cand_ptr[0] = 0, cand_ptr[Q] = C).
