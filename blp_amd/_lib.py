@@ -34,6 +34,8 @@ SYMBOLS = ("blp_version", "blp_last_error", "blp_device_caps", "blp_selftest", "
            "blp_topk_sets_supported", "blp_topk_sets_workspace_bytes", "blp_topk_sets",
            "blp_topk_sets_typed_supported", "blp_topk_sets_typed_workspace_bytes", "blp_topk_sets_typed",
            "blp_topk_lists_supported", "blp_topk_lists_workspace_bytes", "blp_topk_lists",
+           "blp_rank_relations_supported", "blp_rank_relations_workspace_bytes", "blp_rank_relations",
+           "blp_topk_relations_supported", "blp_topk_relations_workspace_bytes", "blp_topk_relations",
            "blp_rerank_supported", "blp_rerank_cosine", "blp_rerank_ndcg")
 HOOK_SYMBOLS = ("blp_debug_set_knob", "blp_debug_gemm_dump", "blp_debug_reset_selftest")  # libblp_hip.hooks.so only
 KNOBS = ("rank_kernel", "gemm_kernel", "sad_queries_per_group", "sad_pass_groups", "sad_min_queries",
@@ -255,6 +257,20 @@ def _load(path, hooks):
     L.blp_topk_lists.restype = _i
     L.blp_topk_lists.argtypes = [_i, _vp, _i, _i64, _i, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i,
                                  ctypes.POINTER(BlpFilter), _vp, _vp, _vp, _sz, _i, _vp]
+    L.blp_rank_relations_supported.restype = _i
+    L.blp_rank_relations_supported.argtypes = [_i, _i]
+    L.blp_rank_relations_workspace_bytes.restype = _sz
+    L.blp_rank_relations_workspace_bytes.argtypes = [_i, _i, _i64, _i64]
+    L.blp_rank_relations.restype = _i
+    L.blp_rank_relations.argtypes = [_i, _vp, _i64, _i, _i64, _vp, _vp, _i64, _vp, _i64, _vp, ctypes.POINTER(BlpFilter), _vp, _vp, _i64,
+                                     _vp, _sz, _i, _vp]
+    L.blp_topk_relations_supported.restype = _i
+    L.blp_topk_relations_supported.argtypes = [_i, _i, _i]
+    L.blp_topk_relations_workspace_bytes.restype = _sz
+    L.blp_topk_relations_workspace_bytes.argtypes = [_i, _i, _i64, _i64, _i]
+    L.blp_topk_relations.restype = _i
+    L.blp_topk_relations.argtypes = [_i, _vp, _i64, _i, _i64, _vp, _vp, _i64, _vp, _i64, _i, ctypes.POINTER(BlpFilter), _vp, _vp, _vp, _sz,
+                                     _i, _vp]
     L.blp_rerank_supported.restype = _i
     L.blp_rerank_supported.argtypes = [_i64, _i]
     L.blp_rerank_cosine.restype = _i

@@ -892,6 +892,103 @@ int blp_topk_lists(int model, const void* table, int table_dtype, int64_t N, int
     return BLP_OK;
 }
 
+// ---- relation prediction: (h, ?, t) against every row of rel_emb (rank_rels.hip)
+int blp_rank_relations_supported(int model, int D) { return valid_model(model) && blp::rank_relations_supported(model, D) ? 1 : 0; }
+
+size_t blp_rank_relations_workspace_bytes(int model, int D, int64_t Q, int64_t R) {
+    if (!blp_rank_relations_supported(model, D) || Q < 0 || Q > (1ll << 30) || R < 1 || R >= (1ll << 31)) return 0;
+    return blp::rank_relations_workspace_bytes(Q);
+}
+
+int blp_topk_relations_supported(int model, int D, int k) {
+    return valid_model(model) && blp::topk_relations_supported(model, D, k) ? 1 : 0;
+}
+
+size_t blp_topk_relations_workspace_bytes(int model, int D, int64_t Q, int64_t R, int k) {
+    (void)model; (void)D; (void)Q; (void)R; (void)k;
+    return 0;  // the lists live in LDS and every query has one owner: nothing to merge
+}
+
+namespace {
+
+// what the two relation entries check alike: the queries, the candidates, the filter (its values are relation ids)
+int check_relation_call(const char* who, int D, const float* source, int64_t S, int64_t ld_src, const int64_t* head_row,
+                        const int64_t* tail_row, int64_t Q, const float* rel_emb, int64_t R, const blp_filter* filter,
+                        blp::FilterSpec* spec) {
+    if (Q < 0 || S < 0 || ld_src < D)
+        return fail(BLP_ERR_BAD_ARG, "%s: negative size or ld_src < D (Q=%lld S=%lld ld_src=%lld)", who, (long long)Q, (long long)S,
+                    (long long)ld_src);
+    if (R < 1 || R >= (1ll << 31)) return fail(BLP_ERR_BAD_ARG, "%s: R = %lld relations outside [1, 2^31)", who, (long long)R);
+    if (Q > (1ll << 30)) return fail(BLP_ERR_BAD_ARG, "%s: Q = %lld queries, at most 2^30", who, (long long)Q);
+    if (!rel_emb) return fail(BLP_ERR_BAD_ARG, "%s: NULL rel_emb", who);
+    if (Q > 0 && (!source || !head_row || !tail_row || S <= 0))
+        return fail(BLP_ERR_BAD_ARG, "%s: NULL source / head_row / tail_row, or S <= 0", who);
+    if (!aligned16(source) || (ld_src & 3) || !aligned16(rel_emb))
+        return fail(BLP_ERR_BAD_ARG, "%s: source / rel_emb must be 16-byte aligned, ld_src %% 4 == 0", who);
+    if (filter) {
+        if (!filter->seg_lo || !filter->seg_hi || !filter->values)
+            return fail(BLP_ERR_BAD_ARG, "%s: filter needs seg_lo, seg_hi and values", who);
+        if (filter->ent2idx || filter->row_base != 0)
+            return fail(BLP_ERR_BAD_ARG, "%s: the filter's values are relation ids: ent2idx must be NULL and row_base 0 (got row_base %lld)",
+                        who, (long long)filter->row_base);
+        spec->lo = filter->seg_lo; spec->hi = filter->seg_hi; spec->val = filter->values; spec->exclude = filter->exclude;
+    }
+    return BLP_OK;
+}
+
+}  // namespace
+
+int blp_rank_relations(int model, const float* source, int64_t S, int D, int64_t ld_src, const int64_t* head_row, const int64_t* tail_row,
+                       int64_t Q, const float* rel_emb, int64_t R, const int64_t* true_rel, const blp_filter* filter, int32_t* counts,
+                       float* scores, int64_t ld_scores, void* workspace, size_t workspace_bytes, int device, void* stream) {
+    const char* who = "blp_rank_relations";
+    if (!valid_model(model)) return fail(BLP_ERR_BAD_ARG, "%s: unknown model %d", who, model);
+    if (!blp_rank_relations_supported(model, D))
+        return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (64 / 128 / 256: see blp_rank_relations_supported)", who, D);
+    blp::FilterSpec spec;
+    const int st = check_relation_call(who, D, source, S, ld_src, head_row, tail_row, Q, rel_emb, R, filter, &spec);
+    if (st != BLP_OK) return st;
+    if (!counts && !scores) return fail(BLP_ERR_BAD_ARG, "%s: both outputs NULL (give counts, scores or both)", who);
+    if (counts && !true_rel) return fail(BLP_ERR_BAD_ARG, "%s: counts need true_rel (they are taken against the true relation's score)", who);
+    if (scores && ld_scores < R)
+        return fail(BLP_ERR_BAD_ARG, "%s: ld_scores = %lld < R = %lld", who, (long long)ld_scores, (long long)R);
+    if (!aligned16(counts) || !aligned16(scores)) return fail(BLP_ERR_BAD_ARG, "%s: counts / scores must be 16-byte aligned", who);
+    if (Q == 0) return BLP_OK;
+    const size_t need = counts ? blp::rank_relations_workspace_bytes(Q) : 0;
+    if (need && (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255u)))
+        return fail(BLP_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned and >= %zu bytes (got %zu)", who, need, workspace_bytes);
+    DeviceGuard guard(device);
+    if (guard.error() != hipSuccess) return hip_fail(guard.error(), "hipSetDevice");
+    hipError_t err = blp::launch_rank_relations(model, D, source, ld_src, head_row, tail_row, Q, rel_emb, R, counts ? true_rel : nullptr, spec,
+                                                counts, scores, ld_scores, workspace, static_cast<hipStream_t>(stream));
+    if (err != hipSuccess) return hip_fail(err, "blp_rank_relations launch");
+    return BLP_OK;
+}
+
+int blp_topk_relations(int model, const float* source, int64_t S, int D, int64_t ld_src, const int64_t* head_row, const int64_t* tail_row,
+                       int64_t Q, const float* rel_emb, int64_t R, int k, const blp_filter* filter, int64_t* rels, float* scores,
+                       void* workspace, size_t workspace_bytes, int device, void* stream) {
+    const char* who = "blp_topk_relations";
+    (void)workspace; (void)workspace_bytes;  // blp_topk_relations_workspace_bytes() == 0
+    if (!valid_model(model)) return fail(BLP_ERR_BAD_ARG, "%s: unknown model %d", who, model);
+    if (k < 1 || k > 256) return fail(BLP_ERR_BAD_ARG, "%s: k = %d outside [1, 256]", who, k);
+    if (!blp_topk_relations_supported(model, D, k))
+        return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (64 / 128 / 256: see blp_topk_relations_supported)", who, D);
+    blp::FilterSpec spec;
+    const int st = check_relation_call(who, D, source, S, ld_src, head_row, tail_row, Q, rel_emb, R, filter, &spec);
+    if (st != BLP_OK) return st;
+    if (Q >= ((1ll << 31) + k - 1) / k) return fail(BLP_ERR_BAD_ARG, "%s: Q x k must stay below 2^31", who);
+    if (!rels || !scores) return fail(BLP_ERR_BAD_ARG, "%s: NULL rels / scores", who);
+    if (!aligned16(rels) || !aligned16(scores)) return fail(BLP_ERR_BAD_ARG, "%s: rels / scores must be 16-byte aligned", who);
+    if (Q == 0) return BLP_OK;
+    DeviceGuard guard(device);
+    if (guard.error() != hipSuccess) return hip_fail(guard.error(), "hipSetDevice");
+    hipError_t err = blp::launch_topk_relations(model, D, source, ld_src, head_row, tail_row, Q, rel_emb, R, k, spec, rels, scores,
+                                                static_cast<hipStream_t>(stream));
+    if (err != hipSuccess) return hip_fail(err, "blp_topk_relations launch");
+    return BLP_OK;
+}
+
 // ---- candidate sets shared between queries (rank_sets.hip)
 int blp_rank_sets_supported(int model, int D) { return valid_model(model) && blp::rank_sets_supported(model, D) ? 1 : 0; }
 

@@ -129,6 +129,20 @@ hipError_t launch_topk_lists(int model, int D, int dtype, const void* table, int
                              const int64_t* list_row, int64_t nnz, int k, const FilterSpec& filter, int64_t* rows, float* scores,
                              void* workspace, hipStream_t stream);
 
+// rank_rels.hip: relation prediction (include/blp_hip.h: blp_rank_relations, blp_topk_relations): query q = rows head_row[q],
+// tail_row[q] of `source`; the candidates are all R rows of rel_emb (contiguous); the filter's values are relation ids.
+// counts and / or scores (Q, R; row stride ld_scores); the workspace holds the true keys (needed with counts only).  The top-k
+// call needs no workspace.
+bool rank_relations_supported(int model, int D);
+size_t rank_relations_workspace_bytes(int64_t Q);
+hipError_t launch_rank_relations(int model, int D, const float* source, int64_t ld_src, const int64_t* head_row, const int64_t* tail_row,
+                                 int64_t Q, const float* rel_emb, int64_t R, const int64_t* true_rel, const FilterSpec& filter,
+                                 int32_t* counts, float* scores, int64_t ld_scores, void* workspace, hipStream_t stream);
+bool topk_relations_supported(int model, int D, int k);
+hipError_t launch_topk_relations(int model, int D, const float* source, int64_t ld_src, const int64_t* head_row, const int64_t* tail_row,
+                                 int64_t Q, const float* rel_emb, int64_t R, int k, const FilterSpec& filter, int64_t* rels, float* scores,
+                                 hipStream_t stream);
+
 // rerank.hip: re-ranking a retrieval run (include/blp_hip.h: blp_rerank_cosine, blp_rerank_ndcg)
 constexpr int kRerankMaxSegment = 8192;  // candidates per query: 8 192 keys of 8 bytes = 64 KiB of LDS
 constexpr int kRerankMaxCutoffs = 8;

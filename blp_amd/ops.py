@@ -726,6 +726,121 @@ def topk_lists(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, li
     return rows, scores
 
 
+def rank_relations_supported(rel_model, dim):
+    """True if rank_relations takes this width (include/blp_hip.h: blp_rank_relations_supported -- the four models at 64 / 128 /
+    256)."""
+    return bool(_lib.lib().blp_rank_relations_supported(_lib.MODEL_IDS[rel_model], int(dim)))
+
+
+def rank_relations_workspace_bytes(rel_model, D, Q, R):
+    """Bytes of rank_relations' workspace: the Q true-relation scores (4 Q rounded up to 256), whatever R."""
+    return int(_lib.lib().blp_rank_relations_workspace_bytes(_lib.MODEL_IDS[rel_model], int(D), int(Q), int(R)))
+
+
+def topk_relations_supported(rel_model, dim, k):
+    """True if topk_relations takes this width and k (rank_relations' widths, 1 <= k <= 256)."""
+    return bool(_lib.lib().blp_topk_relations_supported(_lib.MODEL_IDS[rel_model], int(dim), int(k)))
+
+
+def topk_relations_workspace_bytes(rel_model, D, Q, R, k):
+    """Bytes of topk_relations' workspace: 0 (the lists live on chip, every query has one owner)."""
+    return int(_lib.lib().blp_topk_relations_workspace_bytes(_lib.MODEL_IDS[rel_model], int(D), int(Q), int(R), int(k)))
+
+
+def _relation_queries(source, head_row, tail_row, rel_emb, who):
+    _require_device(source, head_row, tail_row, rel_emb)
+    if source.dtype != torch.float32:
+        raise TypeError(f"{who} needs a float32 `source` for the queries' vectors, got {source.dtype} (gather and widen a 16-bit "
+                        "table's rows with gather_triple_vectors)")
+    source = _f32_rows(source, "source")
+    rel_emb = _f32_rows(rel_emb, "rel_emb").contiguous()
+    if source.dim() != 2 or rel_emb.dim() != 2 or rel_emb.shape[1] != source.shape[1] or rel_emb.shape[0] < 1:
+        raise ValueError(f"source must be (S, D) and rel_emb (R >= 1, D), got {tuple(source.shape)} and {tuple(rel_emb.shape)}")
+    head_row, tail_row = _i64_vector(head_row), _i64_vector(tail_row)
+    if head_row.shape[0] != tail_row.shape[0]:
+        raise ValueError("head_row and tail_row need one entry per query")
+    return source, head_row, tail_row, rel_emb
+
+
+def rank_relations(rel_model, source, head_row, tail_row, rel_emb, true_rel=None, filter=None, return_scores=False, out=None):
+    """Relation prediction, ranking form (blp_rank_relations): query q is the pair (row head_row[q], row tail_row[q]) of ``source``
+    (S, D) float32; the candidates are all R rows of ``rel_emb``.  With ``true_rel`` (Q,): counts (Q, 4) int32 = {gt, ge, gt_filt,
+    ge_filt}, the relations that score above / at least the true one, the last two without those ``filter`` (a SegmentFilter
+    whose values are RELATION ids: no ent2idx, row_base 0; ``exclude`` is never removed) names.  ``return_scores``: the (Q, R)
+    score matrix, score_fn's values bit for bit.  Returns counts, scores, or (counts, scores); ``out`` may give counts."""
+    source, head_row, tail_row, rel_emb = _relation_queries(source, head_row, tail_row, rel_emb, "rank_relations")
+    _require_device(true_rel)
+    Q, (R, D) = head_row.shape[0], rel_emb.shape
+    if true_rel is None and not return_scores:
+        raise ValueError("rank_relations: give true_rel (counts), return_scores=True, or both")
+    if not rank_relations_supported(rel_model, D):
+        raise ValueError(f"rank_relations: D = {D} not supported for {rel_model} (64 / 128 / 256: see rank_relations_supported)")
+    if filter is not None and (filter.ent2idx is not None or int(filter.row_base) != 0):
+        raise ValueError("rank_relations: the filter's values are relation ids (ent2idx None, row_base 0)")
+    dev = source.device
+    counts = scores = None
+    if true_rel is not None:
+        true_rel = _i64_vector(true_rel)
+        if true_rel.shape[0] != Q:
+            raise ValueError("true_rel needs one entry per query")
+        counts = torch.empty((Q, 4), dtype=torch.int32, device=dev) if out is None else out
+        if counts.shape != (Q, 4) or counts.dtype != torch.int32 or not counts.is_contiguous():
+            raise ValueError("out must be a contiguous (Q, 4) int32 tensor")
+    if return_scores:
+        scores = torch.empty((Q, R), dtype=torch.float32, device=dev)
+    if Q:
+        L = _lib.lib()
+        model = _lib.MODEL_IDS[rel_model]
+        stream = torch._C._cuda_getCurrentRawStream(dev.index)
+        ws_bytes = L.blp_rank_relations_workspace_bytes(model, D, Q, R) if counts is not None else 0
+        workspace = _workspace(dev, stream, ws_bytes) if ws_bytes else None
+        spec = None if filter is None else _filter_spec(filter, Q, dev)
+        status = L.blp_rank_relations(model, source.data_ptr(), source.shape[0], D, source.stride(0) if source.shape[0] > 1 else D,
+                                      head_row.data_ptr(), tail_row.data_ptr(), Q, rel_emb.data_ptr(), R, _addr(true_rel), spec,
+                                      _addr(counts), _addr(scores), R, _addr(workspace), ws_bytes, dev.index, stream)
+        if status:
+            _lib.check(status, "blp_rank_relations")
+    if counts is None:
+        return scores
+    return (counts, scores) if return_scores else counts
+
+
+def topk_relations(rel_model, source, head_row, tail_row, rel_emb, k, filter=None, out=None):
+    """Relation prediction, answer form (blp_topk_relations): per pair (row head_row[q], row tail_row[q]) of ``source`` the k
+    relations with the highest score_fn value in topk's order (descending score, ties by ascending relation id, NaN last), the
+    relations ``filter`` names removed (a SegmentFilter of relation ids, as in rank_relations); slots beyond the relations left
+    (k > R, a filter that leaves fewer): -1, score NaN.  Returns (rels (Q, k) int64, scores (Q, k) float32); ``out`` may give
+    both."""
+    source, head_row, tail_row, rel_emb = _relation_queries(source, head_row, tail_row, rel_emb, "topk_relations")
+    Q, (R, D) = head_row.shape[0], rel_emb.shape
+    k = int(k)
+    if not topk_relations_supported(rel_model, D, k):
+        raise ValueError(f"topk_relations: D = {D}, k = {k} not supported for {rel_model} (64 / 128 / 256, 1 <= k <= 256)")
+    if filter is not None and (filter.ent2idx is not None or int(filter.row_base) != 0):
+        raise ValueError("topk_relations: the filter's values are relation ids (ent2idx None, row_base 0)")
+    dev = source.device
+    if out is None:
+        out = (torch.empty((Q, k), dtype=torch.int64, device=dev), torch.empty((Q, k), dtype=torch.float32, device=dev))
+    rels, scores = out
+    if rels.shape != (Q, k) or rels.dtype != torch.int64 or not rels.is_contiguous() or scores.shape != (Q, k) or \
+            scores.dtype != torch.float32 or not scores.is_contiguous():
+        raise ValueError("out must be contiguous (Q, k) int64 relation ids and (Q, k) float32 scores")
+    if Q == 0:
+        return rels, scores
+    L = _lib.lib()
+    model = _lib.MODEL_IDS[rel_model]
+    stream = torch._C._cuda_getCurrentRawStream(dev.index)
+    ws_bytes = L.blp_topk_relations_workspace_bytes(model, D, Q, R, k)
+    workspace = _workspace(dev, stream, ws_bytes) if ws_bytes else None
+    spec = None if filter is None else _filter_spec(filter, Q, dev)
+    status = L.blp_topk_relations(model, source.data_ptr(), source.shape[0], D, source.stride(0) if source.shape[0] > 1 else D,
+                                  head_row.data_ptr(), tail_row.data_ptr(), Q, rel_emb.data_ptr(), R, k, spec, rels.data_ptr(),
+                                  scores.data_ptr(), _addr(workspace), ws_bytes, dev.index, stream)
+    if status:
+        _lib.check(status, "blp_topk_relations")
+    return rels, scores
+
+
 def topk_merge(rows, scores, k):
     """The k best of per-query candidate lists (blp_topk_merge): rows (Q, n) int64 global rows (< 0: an empty slot) and
     scores (Q, n) float32 -- e.g. the topk results of several candidate shards side by side -- in topk's order.

@@ -907,6 +907,114 @@ def predict_from_candidates(model, table, triples, k, candidates, ent2idx, *, si
     return out_rows, scores
 
 
+# ----------------------------------------------------------------------------------- relation prediction: (h, ?, t)
+def _relation_scores_dense(score_fn, head_vecs, tail_vecs, rel_w, max_bytes=1 << 28):
+    """The reference's route for (h, ?, t): score_fn broadcast over every relation, in query pieces whose (piece, R, D)
+    intermediate stays within ``max_bytes``.  Yields (lo, hi, (hi - lo, R) scores)."""
+    Q, (R, D) = head_vecs.shape[0], rel_w.shape
+    piece = max(1, min(max(Q, 1), max_bytes // max(4 * R * D, 1)))
+    rels = rel_w.unsqueeze(0)
+    for lo in range(0, Q, piece):
+        hi = min(lo + piece, Q)
+        yield lo, hi, score_fn(head_vecs[lo:hi].unsqueeze(1), tail_vecs[lo:hi].unsqueeze(1), rels)
+
+
+def _relation_queries(model, table, triples, ent2idx, who, min_cols):
+    """(triples on the table's device, head rows, tail rows, rel_emb weight) of a relation-prediction call."""
+    device = table.device
+    triples = triples.to(device=device, dtype=torch.long)
+    if triples.dim() != 2 or not min_cols <= triples.shape[1] <= 3:
+        raise ValueError(f"{who}: rows of {'(head, tail, rel)' if min_cols == 3 else '(head, tail) or (head, tail, rel)'} "
+                         f"entity ids expected, got shape {tuple(triples.shape)}")
+    ent2idx = ent2idx.to(device=device, dtype=torch.long)
+    ids = triples[:, :2]
+    known = (ids >= 0) & (ids < ent2idx.shape[0])
+    rows = torch.where(known, ent2idx[torch.where(known, ids, torch.zeros_like(ids))], torch.full_like(ids, -1))
+    rel_w = model.rel_emb.weight.detach()
+    if triples.shape[0] and bool(((rows < 0) | (rows >= table.shape[0])).any()):
+        raise ValueError(f"{who}: an entity of a pair has no table row")
+    if triples.shape[1] == 3 and triples.shape[0]:
+        r = triples[:, 2]
+        if bool((r >= rel_w.shape[0]).any()) or (min_cols == 3 and bool((r < 0).any())):
+            raise ValueError(f"{who}: a relation id is out of range")
+    return triples, rows[:, 0].contiguous(), rows[:, 1].contiguous(), rel_w
+
+
+def _relation_source(table, triples, ent2idx, head_rows, tail_rows):
+    """The f32 source of the fused route: the table itself, or -- a 16-bit table -- its 2 T query rows gathered and widened."""
+    if table.dtype == torch.float32:
+        return table, head_rows, tail_rows
+    T = triples.shape[0]
+    if triples.shape[1] == 2:  # (the gather reads (head, tail, rel) rows)
+        triples = torch.cat((triples, torch.zeros_like(triples[:, :1])), 1)
+    both = ops.gather_triple_vectors(triples, ent2idx.to(device=table.device, dtype=torch.long), table)
+    at = torch.arange(T, device=table.device)
+    return both, at, at + T
+
+
+def rank_relations(model, table, triples, ent2idx, *, filter_index=None, return_scores=False):
+    """Rank the true relation of every triple (head, tail, rel) of ``triples`` (T, 3) entity / relation ids among ALL relations
+    of the model, for the pair (head, ?, tail).
+    table        (N, D) entity table (build_entity_table), float32 / float16 / bfloat16 (16-bit rows are widened exactly)
+    ent2idx      utils.make_ent2idx map; both entities of every triple must have a row
+    filter_index utils.RelationFilterIndex of the known edges: the other known relations of the pair leave the filtered counts
+    Returns counts (T, 4) int32 = {gt, ge, gt_filt, ge_filt} -- relations scoring above / at least the true one, IEEE
+    comparison, the true relation itself included in ge; metrics_from_counts applies unchanged -- and, with ``return_scores``,
+    the (T, R) score_fn values bit for bit.  HIP tensors at a width blp_rank_relations takes: the fused kernel (no (T, R)
+    matrix unless asked for); CPU tensors and other widths: score_fn broadcast over the relations in bounded pieces."""
+    model = _module(model)
+    triples, head_rows, tail_rows, rel_w = _relation_queries(model, table, triples, ent2idx, "rank_relations", 3)
+    device, T, R = table.device, triples.shape[0], rel_w.shape[0]
+    filt = filter_index.segments(triples, device) if filter_index is not None and T else None
+    if table.is_cuda and ops.rank_relations_supported(model.rel_model, table.shape[1]):
+        source, hr, tr = _relation_source(table, triples, ent2idx, head_rows, tail_rows)
+        return ops.rank_relations(model.rel_model, source, hr, tr, rel_w, triples[:, 2].contiguous(), filter=filt,
+                                  return_scores=return_scores)
+    counts = torch.empty((T, 4), dtype=torch.int32, device=device)
+    scores = torch.empty((T, R), dtype=torch.float32, device=device) if return_scores else None
+    dense_filt = None if filt is None else (filt.seg_lo, filt.seg_hi, filt.values, filt.exclude, None)
+    for lo, hi, s in _relation_scores_dense(model.score_fn, table[head_rows].float(), table[tail_rows].float(), rel_w):
+        kt = s.gather(1, triples[lo:hi, 2:3])
+        kept = torch.ones(s.shape, dtype=torch.bool, device=device)
+        owner, local = _filtered_pairs(dense_filt, lo, hi, 0, R, device)
+        kept[owner, local] = False
+        gt, ge = s > kt, s >= kt
+        counts[lo:hi] = torch.stack((gt.sum(1), ge.sum(1), (gt & kept).sum(1), (ge & kept).sum(1)), 1).to(torch.int32)
+        if return_scores:
+            scores[lo:hi] = s
+    return (counts, scores) if return_scores else counts
+
+
+def predict_relations(model, table, pairs, k, ent2idx, *, filter_index=None):
+    """Answer (head, ?, tail): for every row of ``pairs`` -- (head, tail) or (head, tail, rel) entity ids -- the k relations
+    the model scores highest.  ``filter_index`` (utils.RelationFilterIndex of the known edges): the known relations of the pair
+    are REMOVED, except the row's third column when there is one (-1 there removes every known relation, as two columns do).
+    Returns (rels (T, k) int64, scores (T, k) float32): descending score, ties by ascending relation id, NaN last; -1 / NaN
+    beyond the relations left (k may exceed R).  Scores are score_fn's values bit for bit.  HIP tensors at a width
+    blp_topk_relations takes and k <= 256: the fused kernel; otherwise score_fn broadcast in bounded pieces + the stable
+    order (also the fused route's oracle)."""
+    model = _module(model)
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"k = {k} must be >= 1")
+    pairs, head_rows, tail_rows, rel_w = _relation_queries(model, table, pairs, ent2idx, "predict_relations", 2)
+    device, T, R = table.device, pairs.shape[0], rel_w.shape[0]
+    filt = filter_index.segments(pairs, device) if filter_index is not None and T else None
+    if table.is_cuda and ops.topk_relations_supported(model.rel_model, table.shape[1], k):
+        source, hr, tr = _relation_source(table, pairs, ent2idx, head_rows, tail_rows)
+        return ops.topk_relations(model.rel_model, source, hr, tr, rel_w, k, filter=filt)
+    rels_out = torch.empty((T, k), dtype=torch.int64, device=device)
+    scores_out = torch.empty((T, k), dtype=torch.float32, device=device)
+    dense_filt = None if filt is None else (filt.seg_lo, filt.seg_hi, filt.values, filt.exclude, None)
+    ids = torch.arange(R, device=device, dtype=torch.int64)
+    for lo, hi, s in _relation_scores_dense(model.score_fn, table[head_rows].float(), table[tail_rows].float(), rel_w):
+        removed = torch.zeros(s.shape, dtype=torch.bool, device=device)
+        owner, local = _filtered_pairs(dense_filt, lo, hi, 0, R, device)
+        removed[owner, local] = True
+        rels_out[lo:hi], scores_out[lo:hi] = _stable_topk(s, ids.expand(hi - lo, R), removed, k)
+    return rels_out, scores_out
+
+
 # ----------------------------------------------------------------------------------- candidate sets shared between queries
 def _sets_from_pairs(owner, rows, num_sets):
     """(ptr (G + 1,), rows (nnz,)) of the sets {rows[i] : owner[i] == g}: each set sorted ascending, duplicates dropped."""

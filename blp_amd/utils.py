@@ -201,6 +201,52 @@ class FilterIndex:
         return mask[:b], mask[b:]
 
 
+class RelationFilterIndex:
+    """Sorted index of a graph by entity PAIR: (head, tail) -> the known relations between them, for relation prediction
+    (ranking.rank_relations / predict_relations).  Built like FilterIndex: one sort + unique of the packed (pair, relation)
+    values with torch ops, on ``device`` when given, else where ``edges`` lives; parallel edges collapse.  ``key`` holds the
+    packed pair head * span + tail of every entry (sorted), ``values`` its relation id (sorted within a pair)."""
+
+    def __init__(self, edges, device=None):
+        """edges: (E, 3) int64 rows (head, tail, rel), the reference's triple column order (data.py:128)."""
+        edges = edges.to(device=device if device is not None else edges.device, dtype=torch.long).reshape(-1, 3)
+        self.home = edges.device
+        self.num_edges = edges.shape[0]
+        self.span = int(edges[:, :2].max()) + 1 if self.num_edges else 1   # entity ids are < span
+        self.R = int(edges[:, 2].max()) + 1 if self.num_edges else 1
+        packed = torch.unique((edges[:, 0] * self.span + edges[:, 1]) * self.R + edges[:, 2])  # sorted, duplicates removed
+        self.key = torch.div(packed, self.R, rounding_mode="floor").contiguous()
+        self.values = (packed % self.R).contiguous()
+
+    def _on(self, device):
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device == self.home:
+            return self.key, self.values
+        cache = self.__dict__.setdefault("_device_cache", {})
+        if device not in cache:
+            cache[device] = (self.key.to(device), self.values.to(device))
+        return cache[device]
+
+    def segments(self, triples, device):
+        """The filter of a batch of pairs as a blp_amd.ops.SegmentFilter of RELATION ids (no ent2idx, row_base 0): query q
+        loses values[seg_lo[q] .. seg_hi[q]), the known relations of (triples[q, 0], triples[q, 1]), except exclude[q] = the
+        row's third column (the relation asked about; -1, which removes every known relation, when there are two columns).
+        Two binary searches on ``device``; an entity id the graph never saw matches nothing."""
+        from .ops import SegmentFilter
+        device = torch.device(device)
+        key, values = self._on(device)
+        triples = triples.to(device=device, dtype=torch.long)
+        h, t = triples[:, 0], triples[:, 1]
+        known = (h >= 0) & (h < self.span) & (t >= 0) & (t < self.span)
+        pair = torch.where(known, h * self.span + t, -1)
+        lo = torch.searchsorted(key, pair, right=False)
+        hi = torch.searchsorted(key, pair, right=True)
+        exclude = triples[:, 2].contiguous() if triples.shape[1] > 2 else torch.full_like(h, -1)
+        return SegmentFilter(lo, hi, values, exclude, None, 0)
+
+
 def get_triple_filters(triples, graph, num_ents, ent2idx):
     """Dense (B, num_ents) bool masks of known-true replacement heads / tails (reference semantics:
     same relation, different entity than the triple's own, candidates only).  ``graph`` may be the

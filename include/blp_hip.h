@@ -703,6 +703,51 @@ int blp_topk_lists(int model, const void *table, int table_dtype, int64_t N, int
                    size_t workspace_bytes, int device, void *stream);
 
 /* --------------------------------------------------------------------------------------------
+ * RELATION prediction: the third question of knowledge-graph completion, (h, ?, t) -- which relation holds between two
+ * entities.  The candidates are the rows of rel_emb; the (Q, R) score matrix is never needed to rank or to predict.
+ *
+ * Queries: query q is the pair (row head_row[q], row tail_row[q]) of source (S, D) f32, row stride ld_src (rows trusted to lie
+ * in [0, S)).  As everywhere in this ABI the queries' vectors are f32: a caller with a 16-bit table gathers and widens them
+ * with blp_gather_triple_vectors.  head_row[q] == tail_row[q] is legal.
+ * Candidates: all R rows of rel_emb (R, D) f32, contiguous.
+ * blp_rank_relations:
+ *   counts (Q, 4) int32 = {gt, ge, gt_filt, ge_filt}: the relations that score above / at least relation true_rel[q] (Q int64,
+ *          trusted to lie in [0, R)) by IEEE comparison.  The true relation is a candidate like any other, so it adds to ge
+ *          (unless its score is NaN); blp_rank_metrics applies unchanged.  counts needs true_rel.
+ *   scores (Q, R) f32, row stride ld_scores >= R: score_fn's value of every (pair, relation) bit for bit (the torch-CPU order
+ *          of oracle/blp_oracle.c, sign of zero included); floats [R, ld_scores) of a row are not touched.
+ *   Either output may be NULL, not both.
+ * blp_topk_relations: rels (Q, k) int64 relation ids, scores (Q, k) f32, in blp_topk's order and padding exactly: descending
+ *   score, equal scores (-0 == +0) by ascending relation id, NaN scores after every number (by id) and written as 0x7fc00000;
+ *   filtered relations are REMOVED; slots left over are -1 / 0x7fc00000; k > R is legal.
+ * Filter (optional): a blp_filter whose `values` are RELATION ids -- ent2idx must be NULL and row_base 0, else
+ *   BLP_ERR_BAD_ARG.  Query q loses the relations values[seg_lo[q] .. seg_hi[q]); an id outside [0, R) is ignored; exclude[q]
+ *   is never removed; a segment's entries are trusted to be distinct.  Filtered relations leave gt_filt / ge_filt.  Segments are
+ *   walked entry by entry per query: they are meant to be the handful of known relations of one pair.
+ * Limits: the four models at D in {64, 128, 256} (blp_rank_relations_supported; the top-k call also 1 <= k <= 256);
+ *   1 <= R < 2^31; Q <= 2^30; Q x k < 2^31; source / rel_emb / outputs 16-byte aligned, ld_src % 4 == 0, ld_src >= D.
+ *   Q = 0 succeeds and touches nothing.  Every check runs before a device is touched.
+ * Workspace, 256-B aligned: blp_rank_relations_workspace_bytes = 4 Q bytes rounded up to 256 (the true relations' scores;
+ *   used with counts only: a scores-only call accepts NULL), whatever R; blp_topk_relations_workspace_bytes = 0 for every Q,
+ *   R, k (the k-lists live in on-chip memory and every query has one owning workgroup: there is nothing to merge), workspace
+ *   may be NULL.
+ * Asynchronous on `stream`, no host synchronisation, no allocation.  Deterministic: counts are integer sums, a top-k result
+ * is the set of the k largest keys; nothing depends on the grid.
+ * (Added after 6.0.0 without a version change: no existing entry point changed.)
+ * -------------------------------------------------------------------------------------------- */
+int blp_rank_relations_supported(int model, int D);
+size_t blp_rank_relations_workspace_bytes(int model, int D, int64_t Q, int64_t R);
+int blp_rank_relations(int model, const float *source, int64_t S, int D, int64_t ld_src, const int64_t *head_row,
+                       const int64_t *tail_row, int64_t Q, const float *rel_emb, int64_t R, const int64_t *true_rel,
+                       const blp_filter *filter, int32_t *counts, float *scores, int64_t ld_scores, void *workspace,
+                       size_t workspace_bytes, int device, void *stream);
+int blp_topk_relations_supported(int model, int D, int k);
+size_t blp_topk_relations_workspace_bytes(int model, int D, int64_t Q, int64_t R, int k);
+int blp_topk_relations(int model, const float *source, int64_t S, int D, int64_t ld_src, const int64_t *head_row,
+                       const int64_t *tail_row, int64_t Q, const float *rel_emb, int64_t R, int k, const blp_filter *filter,
+                       int64_t *rels, float *scores, void *workspace, size_t workspace_bytes, int device, void *stream);
+
+/* --------------------------------------------------------------------------------------------
  * Re-ranking a first-stage retrieval run (reference retrieval.py rerank: BM25F candidates of DBpedia-Entity v2 re-scored
  * with entity embeddings, the mixing weight alpha chosen per fold by nDCG@100).  Candidates are a CSR over Q queries:
  * query q owns candidates [cand_ptr[q], cand_ptr[q + 1]) (cand_ptr (Q + 1) int64, cand_ptr[0] = 0, cand_ptr[Q] = C).

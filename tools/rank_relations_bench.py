@@ -1,0 +1,148 @@
+"""Time relation prediction -- blp_rank_relations (filtered counts) and blp_topk_relations (filtered top-k) -- next to the
+route the library offered before them: ops.score broadcast to a (Q, R) matrix in query pieces of at most 256 MiB, then
+ops.rank_from_scores for the counts or a stable torch sort for the predictions.
+
+For each workload: the same pairs, relations and filter (2 entries per query, never the true relation); the results of the two
+routes are compared before anything is timed; the two calls then alternate step by step in one process, each bracketed by device
+events: --warmup steps, then --steps steps, the median taken; that five times over.  One JSON line per workload: the median of
+the five medians of both routes, their ratio, the spread of the five medians ((max - min) / median) and the fraction of the f32
+lane-op roof (78.6 T lane-ops/s) at 3 lane-ops per (pair, column) -- TransE: add, subtract, add |x|; DistMult: multiply,
+multiply, add.
+
+    python tools/rank_relations_bench.py [--steps 30] [--warmup 3] [--repeats 5] [--only NAME ...] [--out FILE.jsonl]
+
+  fb15k237-{transe,distmult}     310 116 pairs over a 14 541 x 128 table, R = 237
+  wikidata5m-{transe,distmult}   1 000 000 pairs over 100 000 x 128 gathered rows, R = 822
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from blp_amd import ops  # noqa: E402
+
+WORKLOADS = {
+    "fb15k237-transe": dict(model="transe", S=14_541, D=128, Q=310_116, R=237),
+    "fb15k237-distmult": dict(model="distmult", S=14_541, D=128, Q=310_116, R=237),
+    "wikidata5m-transe": dict(model="transe", S=100_000, D=128, Q=1_000_000, R=822),
+    "wikidata5m-distmult": dict(model="distmult", S=100_000, D=128, Q=1_000_000, R=822),
+}
+K = 10
+PIECE_BYTES = 1 << 28
+ROOF_LANE_OPS = 78.6e12
+OPS_PER_COLUMN = 3
+
+
+def measure(calls, steps, warmup):
+    ev = {n: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for n in calls}
+    out = {n: [] for n in calls}
+    for i in range(warmup + steps):
+        for n, fn in calls.items():
+            ev[n][0].record()
+            fn()
+            ev[n][1].record()
+        torch.cuda.synchronize()
+        if i >= warmup:
+            for n in calls:
+                out[n].append(ev[n][0].elapsed_time(ev[n][1]))
+    return {n: float(np.median(v)) for n, v in out.items()}
+
+
+def summary(medians):
+    a = np.asarray(medians)
+    mid = float(np.median(a))
+    return {"median_ms": round(mid, 4), "spread": round(float((a.max() - a.min()) / mid), 4), "medians_ms": [round(float(x), 4) for x in a]}
+
+
+def run(name, cfg, steps, warmup, repeats):
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev).manual_seed(0)
+    S, D, Q, R, model = cfg["S"], cfg["D"], cfg["Q"], cfg["R"], cfg["model"]
+    source = torch.randn((S, D), generator=g, device=dev)
+    source = torch.nn.functional.normalize(source, dim=-1) if model == "transe" else source * 0.1
+    rel_w = torch.randn((R, D), generator=g, device=dev) * 0.1
+    hr = torch.randint(0, S, (Q,), generator=g, device=dev)
+    tr = torch.randint(0, S, (Q,), generator=g, device=dev)
+    true = torch.randint(0, R, (Q,), generator=g, device=dev)
+    u = torch.randint(0, R - 2, (Q,), generator=g, device=dev)
+    cols = torch.stack(((true + 1 + u) % R, (true + 1 + (u + 1) % (R - 1)) % R), 1).reshape(-1).contiguous()  # two others, distinct
+    lo = torch.arange(Q, device=dev) * 2
+    rowptr = torch.arange(Q + 1, device=dev) * 2
+    filt = ops.SegmentFilter(lo, lo + 2, cols, None, None, 0)
+    piece = max(1, PIECE_BYTES // (4 * R))
+    rels = rel_w.unsqueeze(0)
+    owner = torch.arange(Q, device=dev).repeat_interleave(2)
+    res = {}
+
+    def matrix(a, b):
+        return ops.score(model, source[hr[a:b]].unsqueeze(1), source[tr[a:b]].unsqueeze(1), rels)
+
+    def fused_counts():
+        res["fc"] = ops.rank_relations(model, source, hr, tr, rel_w, true, filter=filt)
+
+    def yard_counts():
+        out = torch.empty((Q, 4), dtype=torch.int32, device=dev)
+        for a in range(0, Q, piece):
+            b = min(a + piece, Q)
+            out[a:b] = ops.rank_from_scores(matrix(a, b), true_idx=true[a:b], filt_rowptr=rowptr[a:b + 1] - 2 * a, filt_col=cols[2 * a:2 * b])
+        res["yc"] = out
+
+    def fused_topk():
+        res["ft"] = ops.topk_relations(model, source, hr, tr, rel_w, K, filter=filt)
+
+    def yard_topk():
+        ids = torch.empty((Q, K), dtype=torch.int64, device=dev)
+        val = torch.empty((Q, K), dtype=torch.float32, device=dev)
+        for a in range(0, Q, piece):
+            b = min(a + piece, Q)
+            s = matrix(a, b)
+            s[owner[2 * a:2 * b] - a, cols[2 * a:2 * b]] = float("-inf")  # removed: behind every number (K << R - 2)
+            v, i = torch.sort(s, dim=1, descending=True, stable=True)
+            ids[a:b], val[a:b] = i[:, :K], v[:, :K]
+        res["yt"] = (ids, val)
+
+    for fn in (fused_counts, yard_counts, fused_topk, yard_topk):
+        fn()
+    torch.cuda.synchronize()
+    counts_equal = bool(torch.equal(res["fc"], res["yc"]))
+    topk_equal = bool(torch.equal(res["ft"][0], res["yt"][0]) and torch.equal(res["ft"][1].view(torch.int32), res["yt"][1].view(torch.int32)))
+    runs = [measure({"fused_counts": fused_counts, "yard_counts": yard_counts, "fused_topk": fused_topk, "yard_topk": yard_topk}, steps, warmup)
+            for _ in range(repeats)]
+    s = {n: summary([r[n] for r in runs]) for n in runs[0]}
+    lane_ops = Q * R * D * OPS_PER_COLUMN
+    roof = lambda n: round(lane_ops / (s[n]["median_ms"] * 1e-3) / ROOF_LANE_OPS, 4)
+    return {"workload": name, **cfg, "k": K, "filter_entries_per_query": 2, "steps": steps, "warmup": warmup, "repeats": repeats,
+            "counts_equal_yardstick": counts_equal, "topk_equal_yardstick": topk_equal, **s,
+            "counts_yardstick_over_fused": round(s["yard_counts"]["median_ms"] / s["fused_counts"]["median_ms"], 2),
+            "topk_yardstick_over_fused": round(s["yard_topk"]["median_ms"] / s["fused_topk"]["median_ms"], 2),
+            "counts_roof_fraction": roof("fused_counts"), "topk_roof_fraction": roof("fused_topk")}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--only", nargs="*")
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    for name, cfg in WORKLOADS.items():
+        if args.only and name not in args.only:
+            continue
+        line = json.dumps(run(name, cfg, args.steps, args.warmup, args.repeats))
+        print(line, flush=True)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "a") as fh:
+                fh.write(line + "\n")
+        ops.release_workspaces()
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
