@@ -36,6 +36,8 @@ SYMBOLS = ("blp_version", "blp_last_error", "blp_device_caps", "blp_selftest", "
            "blp_topk_lists_supported", "blp_topk_lists_workspace_bytes", "blp_topk_lists",
            "blp_rank_relations_supported", "blp_rank_relations_workspace_bytes", "blp_rank_relations",
            "blp_topk_relations_supported", "blp_topk_relations_workspace_bytes", "blp_topk_relations",
+           "blp_rank_relations_wide_supported", "blp_rank_relations_wide_workspace_bytes", "blp_rank_relations_wide",
+           "blp_topk_relations_wide_supported", "blp_topk_relations_wide_workspace_bytes", "blp_topk_relations_wide",
            "blp_rerank_supported", "blp_rerank_cosine", "blp_rerank_ndcg")
 HOOK_SYMBOLS = ("blp_debug_set_knob", "blp_debug_gemm_dump", "blp_debug_reset_selftest")  # libblp_hip.hooks.so only
 KNOBS = ("rank_kernel", "gemm_kernel", "sad_queries_per_group", "sad_pass_groups", "sad_min_queries",
@@ -271,6 +273,13 @@ def _load(path, hooks):
     L.blp_topk_relations.restype = _i
     L.blp_topk_relations.argtypes = [_i, _vp, _i64, _i, _i64, _vp, _vp, _i64, _vp, _i64, _i, ctypes.POINTER(BlpFilter), _vp, _vp, _vp, _sz,
                                      _i, _vp]
+    for wide, narrow in ((L.blp_rank_relations_wide_supported, L.blp_rank_relations_supported),
+                         (L.blp_rank_relations_wide_workspace_bytes, L.blp_rank_relations_workspace_bytes),
+                         (L.blp_rank_relations_wide, L.blp_rank_relations),
+                         (L.blp_topk_relations_wide_supported, L.blp_topk_relations_supported),
+                         (L.blp_topk_relations_wide_workspace_bytes, L.blp_topk_relations_workspace_bytes),
+                         (L.blp_topk_relations_wide, L.blp_topk_relations)):  # the narrow calls' signatures, by design
+        wide.restype, wide.argtypes = narrow.restype, list(narrow.argtypes)
     L.blp_rerank_supported.restype = _i
     L.blp_rerank_supported.argtypes = [_i64, _i]
     L.blp_rerank_cosine.restype = _i

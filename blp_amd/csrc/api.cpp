@@ -909,9 +909,27 @@ size_t blp_topk_relations_workspace_bytes(int model, int D, int64_t Q, int64_t R
     return 0;  // the lists live in LDS and every query has one owner: nothing to merge
 }
 
+int blp_rank_relations_wide_supported(int model, int D) {
+    return valid_model(model) && blp::rank_relations_wide_supported(model, D) ? 1 : 0;
+}
+
+size_t blp_rank_relations_wide_workspace_bytes(int model, int D, int64_t Q, int64_t R) {
+    if (!blp_rank_relations_wide_supported(model, D) || Q < 0 || Q > (1ll << 30) || R < 1 || R >= (1ll << 31)) return 0;
+    return blp::rank_relations_workspace_bytes(Q);
+}
+
+int blp_topk_relations_wide_supported(int model, int D, int k) {
+    return valid_model(model) && blp::topk_relations_wide_supported(model, D, k) ? 1 : 0;
+}
+
+size_t blp_topk_relations_wide_workspace_bytes(int model, int D, int64_t Q, int64_t R, int k) {
+    (void)model; (void)D; (void)Q; (void)R; (void)k;
+    return 0;  // as blp_topk_relations: lists in LDS, one owner per query, the winners' scores come out of the keys
+}
+
 namespace {
 
-// what the two relation entries check alike: the queries, the candidates, the filter (its values are relation ids)
+// what the relation entries check alike: the queries, the candidates, the filter (its values are relation ids)
 int check_relation_call(const char* who, int D, const float* source, int64_t S, int64_t ld_src, const int64_t* head_row,
                         const int64_t* tail_row, int64_t Q, const float* rel_emb, int64_t R, const blp_filter* filter,
                         blp::FilterSpec* spec) {
@@ -936,15 +954,15 @@ int check_relation_call(const char* who, int D, const float* source, int64_t S, 
     return BLP_OK;
 }
 
-}  // namespace
-
-int blp_rank_relations(int model, const float* source, int64_t S, int D, int64_t ld_src, const int64_t* head_row, const int64_t* tail_row,
-                       int64_t Q, const float* rel_emb, int64_t R, const int64_t* true_rel, const blp_filter* filter, int32_t* counts,
-                       float* scores, int64_t ld_scores, void* workspace, size_t workspace_bytes, int device, void* stream) {
-    const char* who = "blp_rank_relations";
+// blp_rank_relations and blp_rank_relations_wide: the argument checks (messages under the entry's name `who`), then the launch
+int rank_relations_call(const char* who, bool wide, int model, const float* source, int64_t S, int D, int64_t ld_src,
+                        const int64_t* head_row, const int64_t* tail_row, int64_t Q, const float* rel_emb, int64_t R,
+                        const int64_t* true_rel, const blp_filter* filter, int32_t* counts, float* scores, int64_t ld_scores,
+                        void* workspace, size_t workspace_bytes, int device, void* stream) {
     if (!valid_model(model)) return fail(BLP_ERR_BAD_ARG, "%s: unknown model %d", who, model);
-    if (!blp_rank_relations_supported(model, D))
-        return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (64 / 128 / 256: see blp_rank_relations_supported)", who, D);
+    if (!(wide ? blp_rank_relations_wide_supported(model, D) : blp_rank_relations_supported(model, D)))
+        return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (%s: see %s_supported)", who, D,
+                    wide ? "TransE, D % 4 == 0, 4 <= D <= 1024" : "64 / 128 / 256", who);
     blp::FilterSpec spec;
     const int st = check_relation_call(who, D, source, S, ld_src, head_row, tail_row, Q, rel_emb, R, filter, &spec);
     if (st != BLP_OK) return st;
@@ -959,21 +977,22 @@ int blp_rank_relations(int model, const float* source, int64_t S, int D, int64_t
         return fail(BLP_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned and >= %zu bytes (got %zu)", who, need, workspace_bytes);
     DeviceGuard guard(device);
     if (guard.error() != hipSuccess) return hip_fail(guard.error(), "hipSetDevice");
-    hipError_t err = blp::launch_rank_relations(model, D, source, ld_src, head_row, tail_row, Q, rel_emb, R, counts ? true_rel : nullptr, spec,
-                                                counts, scores, ld_scores, workspace, static_cast<hipStream_t>(stream));
-    if (err != hipSuccess) return hip_fail(err, "blp_rank_relations launch");
+    hipError_t err = (wide ? blp::launch_rank_relations_wide : blp::launch_rank_relations)(
+        model, D, source, ld_src, head_row, tail_row, Q, rel_emb, R, counts ? true_rel : nullptr, spec, counts, scores, ld_scores, workspace,
+        static_cast<hipStream_t>(stream));
+    if (err != hipSuccess) return hip_fail(err, wide ? "blp_rank_relations_wide launch" : "blp_rank_relations launch");
     return BLP_OK;
 }
 
-int blp_topk_relations(int model, const float* source, int64_t S, int D, int64_t ld_src, const int64_t* head_row, const int64_t* tail_row,
-                       int64_t Q, const float* rel_emb, int64_t R, int k, const blp_filter* filter, int64_t* rels, float* scores,
-                       void* workspace, size_t workspace_bytes, int device, void* stream) {
-    const char* who = "blp_topk_relations";
-    (void)workspace; (void)workspace_bytes;  // blp_topk_relations_workspace_bytes() == 0
+// blp_topk_relations and blp_topk_relations_wide (neither uses its workspace: *_workspace_bytes() == 0)
+int topk_relations_call(const char* who, bool wide, int model, const float* source, int64_t S, int D, int64_t ld_src,
+                        const int64_t* head_row, const int64_t* tail_row, int64_t Q, const float* rel_emb, int64_t R, int k,
+                        const blp_filter* filter, int64_t* rels, float* scores, int device, void* stream) {
     if (!valid_model(model)) return fail(BLP_ERR_BAD_ARG, "%s: unknown model %d", who, model);
     if (k < 1 || k > 256) return fail(BLP_ERR_BAD_ARG, "%s: k = %d outside [1, 256]", who, k);
-    if (!blp_topk_relations_supported(model, D, k))
-        return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (64 / 128 / 256: see blp_topk_relations_supported)", who, D);
+    if (!(wide ? blp_topk_relations_wide_supported(model, D, k) : blp_topk_relations_supported(model, D, k)))
+        return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (%s: see %s_supported)", who, D,
+                    wide ? "TransE, D % 4 == 0, 4 <= D <= 1024" : "64 / 128 / 256", who);
     blp::FilterSpec spec;
     const int st = check_relation_call(who, D, source, S, ld_src, head_row, tail_row, Q, rel_emb, R, filter, &spec);
     if (st != BLP_OK) return st;
@@ -983,10 +1002,44 @@ int blp_topk_relations(int model, const float* source, int64_t S, int D, int64_t
     if (Q == 0) return BLP_OK;
     DeviceGuard guard(device);
     if (guard.error() != hipSuccess) return hip_fail(guard.error(), "hipSetDevice");
-    hipError_t err = blp::launch_topk_relations(model, D, source, ld_src, head_row, tail_row, Q, rel_emb, R, k, spec, rels, scores,
-                                                static_cast<hipStream_t>(stream));
-    if (err != hipSuccess) return hip_fail(err, "blp_topk_relations launch");
+    hipError_t err = (wide ? blp::launch_topk_relations_wide : blp::launch_topk_relations)(
+        model, D, source, ld_src, head_row, tail_row, Q, rel_emb, R, k, spec, rels, scores, static_cast<hipStream_t>(stream));
+    if (err != hipSuccess) return hip_fail(err, wide ? "blp_topk_relations_wide launch" : "blp_topk_relations launch");
     return BLP_OK;
+}
+
+}  // namespace
+
+int blp_rank_relations(int model, const float* source, int64_t S, int D, int64_t ld_src, const int64_t* head_row, const int64_t* tail_row,
+                       int64_t Q, const float* rel_emb, int64_t R, const int64_t* true_rel, const blp_filter* filter, int32_t* counts,
+                       float* scores, int64_t ld_scores, void* workspace, size_t workspace_bytes, int device, void* stream) {
+    return rank_relations_call("blp_rank_relations", false, model, source, S, D, ld_src, head_row, tail_row, Q, rel_emb, R, true_rel, filter,
+                               counts, scores, ld_scores, workspace, workspace_bytes, device, stream);
+}
+
+int blp_topk_relations(int model, const float* source, int64_t S, int D, int64_t ld_src, const int64_t* head_row, const int64_t* tail_row,
+                       int64_t Q, const float* rel_emb, int64_t R, int k, const blp_filter* filter, int64_t* rels, float* scores,
+                       void* workspace, size_t workspace_bytes, int device, void* stream) {
+    (void)workspace; (void)workspace_bytes;  // blp_topk_relations_workspace_bytes() == 0
+    return topk_relations_call("blp_topk_relations", false, model, source, S, D, ld_src, head_row, tail_row, Q, rel_emb, R, k, filter, rels,
+                               scores, device, stream);
+}
+
+// ---- ... for TransE at any width (rank_rels_wide.hip): the narrow pair's arguments, checks and codes
+int blp_rank_relations_wide(int model, const float* source, int64_t S, int D, int64_t ld_src, const int64_t* head_row,
+                            const int64_t* tail_row, int64_t Q, const float* rel_emb, int64_t R, const int64_t* true_rel,
+                            const blp_filter* filter, int32_t* counts, float* scores, int64_t ld_scores, void* workspace,
+                            size_t workspace_bytes, int device, void* stream) {
+    return rank_relations_call("blp_rank_relations_wide", true, model, source, S, D, ld_src, head_row, tail_row, Q, rel_emb, R, true_rel,
+                               filter, counts, scores, ld_scores, workspace, workspace_bytes, device, stream);
+}
+
+int blp_topk_relations_wide(int model, const float* source, int64_t S, int D, int64_t ld_src, const int64_t* head_row,
+                            const int64_t* tail_row, int64_t Q, const float* rel_emb, int64_t R, int k, const blp_filter* filter,
+                            int64_t* rels, float* scores, void* workspace, size_t workspace_bytes, int device, void* stream) {
+    (void)workspace; (void)workspace_bytes;  // blp_topk_relations_wide_workspace_bytes() == 0
+    return topk_relations_call("blp_topk_relations_wide", true, model, source, S, D, ld_src, head_row, tail_row, Q, rel_emb, R, k, filter,
+                               rels, scores, device, stream);
 }
 
 // ---- candidate sets shared between queries (rank_sets.hip)

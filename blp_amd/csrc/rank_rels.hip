@@ -25,6 +25,7 @@
 
 #include "launch.h"
 #include "rank_common.h"
+#include "rel_common.h"
 #include "rel_scorer.h"
 #include "score_core.h"
 #include "score_direct.h"
@@ -36,34 +37,6 @@
 namespace blp {
 
 constexpr int kRelChunk = 64;          // queries per workgroup pass of rank_rels: 4 counters each = one per thread
-constexpr int kRelMaxGroups = 1024;    // workgroups of a launch (they stride over the query chunks)
-
-struct RelQueries {
-    const float* source;
-    int64_t ld;
-    const int64_t* head_row;
-    const int64_t* tail_row;
-    __device__ __forceinline__ const float* head(int64_t q) const { return source + head_row[q] * ld; }
-    __device__ __forceinline__ const float* tail(int64_t q) const { return source + tail_row[q] * ld; }
-};
-// (the kernels take the four fields as __restrict__ parameters: the query vectors are then provably untouched by the kernel's
-//  stores, which is what lets a wave-uniform read of them be a scalar load)
-#define REL_QUERY_PARAMS \
-    const float* __restrict__ source, int64_t ld_src, const int64_t* __restrict__ head_row, const int64_t* __restrict__ tail_row
-#define REL_QUERY_ARGS(qs) (qs).source, (qs).ld, (qs).head_row, (qs).tail_row
-
-// Does query q's filter segment remove relation `rel`?  Wave-uniform walk (scalar loads); exclude[q] is never removed, an id
-// outside [0, R) matches no lane.
-__device__ __forceinline__ bool rel_removed(const FilterSpec& f, int64_t q, int64_t rel) {
-    const int64_t lo = f.lo[q], hi = f.hi[q];
-    const int64_t keep = f.exclude ? f.exclude[q] : -1;
-    bool removed = false;
-    for (int64_t c = lo; c < hi; ++c) {
-        const int64_t v = f.val[c];
-        removed |= v == rel && v != keep;
-    }
-    return removed;
-}
 
 // (D a template parameter: score_direct's sums then run from registers -- its run-time-width routine keeps them in scratch)
 template <int MODEL, int D>
@@ -227,8 +200,6 @@ bool topk_relations_supported(int model, int D, int k) { return rank_relations_s
 // the true keys, one float per query (used with counts only)
 size_t rank_relations_workspace_bytes(int64_t Q) { return align_up((size_t)Q * 4, 256); }
 
-static unsigned rel_grid(int64_t n_chunks) { return (unsigned)(n_chunks < kRelMaxGroups ? n_chunks : kRelMaxGroups); }
-
 template <int MODEL, int D>
 static hipError_t rank_rels_impl(const RelQueries& qs, int64_t Q, const float* rel_emb, int64_t R, const int64_t* true_rel,
                                  const FilterSpec& filter, int32_t* counts, float* scores, int64_t ld_scores, void* workspace,
@@ -291,8 +262,6 @@ hipError_t launch_topk_relations(int model, int D, const float* source, int64_t 
 }
 
 #undef BLP_REL_ALL
-#undef REL_QUERY_ARGS
-#undef REL_QUERY_PARAMS
 #undef BLP_REL_MODEL
 
 }  // namespace blp

@@ -762,21 +762,19 @@ def _relation_queries(source, head_row, tail_row, rel_emb, who):
     return source, head_row, tail_row, rel_emb
 
 
-def rank_relations(rel_model, source, head_row, tail_row, rel_emb, true_rel=None, filter=None, return_scores=False, out=None):
-    """Relation prediction, ranking form (blp_rank_relations): query q is the pair (row head_row[q], row tail_row[q]) of ``source``
-    (S, D) float32; the candidates are all R rows of ``rel_emb``.  With ``true_rel`` (Q,): counts (Q, 4) int32 = {gt, ge, gt_filt,
-    ge_filt}, the relations that score above / at least the true one, the last two without those ``filter`` (a SegmentFilter
-    whose values are RELATION ids: no ent2idx, row_base 0; ``exclude`` is never removed) names.  ``return_scores``: the (Q, R)
-    score matrix, score_fn's values bit for bit.  Returns counts, scores, or (counts, scores); ``out`` may give counts."""
-    source, head_row, tail_row, rel_emb = _relation_queries(source, head_row, tail_row, rel_emb, "rank_relations")
+def _rank_relations(wide, rel_model, source, head_row, tail_row, rel_emb, true_rel, filter, return_scores, out):
+    """rank_relations (blp_rank_relations) and rank_relations_wide (blp_rank_relations_wide): one argument handling, two entries."""
+    who = "rank_relations_wide" if wide else "rank_relations"
+    source, head_row, tail_row, rel_emb = _relation_queries(source, head_row, tail_row, rel_emb, who)
     _require_device(true_rel)
     Q, (R, D) = head_row.shape[0], rel_emb.shape
     if true_rel is None and not return_scores:
-        raise ValueError("rank_relations: give true_rel (counts), return_scores=True, or both")
-    if not rank_relations_supported(rel_model, D):
-        raise ValueError(f"rank_relations: D = {D} not supported for {rel_model} (64 / 128 / 256: see rank_relations_supported)")
+        raise ValueError(f"{who}: give true_rel (counts), return_scores=True, or both")
+    if not (rank_relations_wide_supported if wide else rank_relations_supported)(rel_model, D):
+        raise ValueError(f"{who}: D = {D} not supported for {rel_model} "
+                         f"({'transe, D % 4 == 0, 4 <= D <= 1024' if wide else '64 / 128 / 256'}: see {who}_supported)")
     if filter is not None and (filter.ent2idx is not None or int(filter.row_base) != 0):
-        raise ValueError("rank_relations: the filter's values are relation ids (ent2idx None, row_base 0)")
+        raise ValueError(f"{who}: the filter's values are relation ids (ent2idx None, row_base 0)")
     dev = source.device
     counts = scores = None
     if true_rel is not None:
@@ -790,34 +788,33 @@ def rank_relations(rel_model, source, head_row, tail_row, rel_emb, true_rel=None
         scores = torch.empty((Q, R), dtype=torch.float32, device=dev)
     if Q:
         L = _lib.lib()
+        entry = "blp_rank_relations_wide" if wide else "blp_rank_relations"
         model = _lib.MODEL_IDS[rel_model]
         stream = torch._C._cuda_getCurrentRawStream(dev.index)
-        ws_bytes = L.blp_rank_relations_workspace_bytes(model, D, Q, R) if counts is not None else 0
+        ws_bytes = getattr(L, entry + "_workspace_bytes")(model, D, Q, R) if counts is not None else 0
         workspace = _workspace(dev, stream, ws_bytes) if ws_bytes else None
         spec = None if filter is None else _filter_spec(filter, Q, dev)
-        status = L.blp_rank_relations(model, source.data_ptr(), source.shape[0], D, source.stride(0) if source.shape[0] > 1 else D,
-                                      head_row.data_ptr(), tail_row.data_ptr(), Q, rel_emb.data_ptr(), R, _addr(true_rel), spec,
-                                      _addr(counts), _addr(scores), R, _addr(workspace), ws_bytes, dev.index, stream)
+        status = getattr(L, entry)(model, source.data_ptr(), source.shape[0], D, source.stride(0) if source.shape[0] > 1 else D,
+                                   head_row.data_ptr(), tail_row.data_ptr(), Q, rel_emb.data_ptr(), R, _addr(true_rel), spec,
+                                   _addr(counts), _addr(scores), R, _addr(workspace), ws_bytes, dev.index, stream)
         if status:
-            _lib.check(status, "blp_rank_relations")
+            _lib.check(status, entry)
     if counts is None:
         return scores
     return (counts, scores) if return_scores else counts
 
 
-def topk_relations(rel_model, source, head_row, tail_row, rel_emb, k, filter=None, out=None):
-    """Relation prediction, answer form (blp_topk_relations): per pair (row head_row[q], row tail_row[q]) of ``source`` the k
-    relations with the highest score_fn value in topk's order (descending score, ties by ascending relation id, NaN last), the
-    relations ``filter`` names removed (a SegmentFilter of relation ids, as in rank_relations); slots beyond the relations left
-    (k > R, a filter that leaves fewer): -1, score NaN.  Returns (rels (Q, k) int64, scores (Q, k) float32); ``out`` may give
-    both."""
-    source, head_row, tail_row, rel_emb = _relation_queries(source, head_row, tail_row, rel_emb, "topk_relations")
+def _topk_relations(wide, rel_model, source, head_row, tail_row, rel_emb, k, filter, out):
+    """topk_relations (blp_topk_relations) and topk_relations_wide (blp_topk_relations_wide)."""
+    who = "topk_relations_wide" if wide else "topk_relations"
+    source, head_row, tail_row, rel_emb = _relation_queries(source, head_row, tail_row, rel_emb, who)
     Q, (R, D) = head_row.shape[0], rel_emb.shape
     k = int(k)
-    if not topk_relations_supported(rel_model, D, k):
-        raise ValueError(f"topk_relations: D = {D}, k = {k} not supported for {rel_model} (64 / 128 / 256, 1 <= k <= 256)")
+    if not (topk_relations_wide_supported if wide else topk_relations_supported)(rel_model, D, k):
+        raise ValueError(f"{who}: D = {D}, k = {k} not supported for {rel_model} "
+                         f"({'transe, D % 4 == 0, 4 <= D <= 1024' if wide else '64 / 128 / 256'}, 1 <= k <= 256)")
     if filter is not None and (filter.ent2idx is not None or int(filter.row_base) != 0):
-        raise ValueError("topk_relations: the filter's values are relation ids (ent2idx None, row_base 0)")
+        raise ValueError(f"{who}: the filter's values are relation ids (ent2idx None, row_base 0)")
     dev = source.device
     if out is None:
         out = (torch.empty((Q, k), dtype=torch.int64, device=dev), torch.empty((Q, k), dtype=torch.float32, device=dev))
@@ -828,17 +825,69 @@ def topk_relations(rel_model, source, head_row, tail_row, rel_emb, k, filter=Non
     if Q == 0:
         return rels, scores
     L = _lib.lib()
+    entry = "blp_topk_relations_wide" if wide else "blp_topk_relations"
     model = _lib.MODEL_IDS[rel_model]
     stream = torch._C._cuda_getCurrentRawStream(dev.index)
-    ws_bytes = L.blp_topk_relations_workspace_bytes(model, D, Q, R, k)
+    ws_bytes = getattr(L, entry + "_workspace_bytes")(model, D, Q, R, k)
     workspace = _workspace(dev, stream, ws_bytes) if ws_bytes else None
     spec = None if filter is None else _filter_spec(filter, Q, dev)
-    status = L.blp_topk_relations(model, source.data_ptr(), source.shape[0], D, source.stride(0) if source.shape[0] > 1 else D,
-                                  head_row.data_ptr(), tail_row.data_ptr(), Q, rel_emb.data_ptr(), R, k, spec, rels.data_ptr(),
-                                  scores.data_ptr(), _addr(workspace), ws_bytes, dev.index, stream)
+    status = getattr(L, entry)(model, source.data_ptr(), source.shape[0], D, source.stride(0) if source.shape[0] > 1 else D,
+                               head_row.data_ptr(), tail_row.data_ptr(), Q, rel_emb.data_ptr(), R, k, spec, rels.data_ptr(),
+                               scores.data_ptr(), _addr(workspace), ws_bytes, dev.index, stream)
     if status:
-        _lib.check(status, "blp_topk_relations")
+        _lib.check(status, entry)
     return rels, scores
+
+
+def rank_relations(rel_model, source, head_row, tail_row, rel_emb, true_rel=None, filter=None, return_scores=False, out=None):
+    """Relation prediction, ranking form (blp_rank_relations): query q is the pair (row head_row[q], row tail_row[q]) of ``source``
+    (S, D) float32; the candidates are all R rows of ``rel_emb``.  With ``true_rel`` (Q,): counts (Q, 4) int32 = {gt, ge, gt_filt,
+    ge_filt}, the relations that score above / at least the true one, the last two without those ``filter`` (a SegmentFilter
+    whose values are RELATION ids: no ent2idx, row_base 0; ``exclude`` is never removed) names.  ``return_scores``: the (Q, R)
+    score matrix, score_fn's values bit for bit.  Returns counts, scores, or (counts, scores); ``out`` may give counts."""
+    return _rank_relations(False, rel_model, source, head_row, tail_row, rel_emb, true_rel, filter, return_scores, out)
+
+
+def topk_relations(rel_model, source, head_row, tail_row, rel_emb, k, filter=None, out=None):
+    """Relation prediction, answer form (blp_topk_relations): per pair (row head_row[q], row tail_row[q]) of ``source`` the k
+    relations with the highest score_fn value in topk's order (descending score, ties by ascending relation id, NaN last), the
+    relations ``filter`` names removed (a SegmentFilter of relation ids, as in rank_relations); slots beyond the relations left
+    (k > R, a filter that leaves fewer): -1, score NaN.  Returns (rels (Q, k) int64, scores (Q, k) float32); ``out`` may give
+    both."""
+    return _topk_relations(False, rel_model, source, head_row, tail_row, rel_emb, k, filter, out)
+
+
+def rank_relations_wide_supported(rel_model, dim):
+    """True if rank_relations_wide takes this width (blp_rank_relations_wide_supported: transe, D % 4 == 0, 4 <= D <= 1024 -- the
+    BOW / DKRL encoders' 300 and 768 among them)."""
+    return bool(_lib.lib().blp_rank_relations_wide_supported(_lib.MODEL_IDS[rel_model], int(dim)))
+
+
+def rank_relations_wide_workspace_bytes(rel_model, D, Q, R):
+    """Bytes of rank_relations_wide's workspace: the Q true-relation scores (4 Q rounded up to 256), whatever R and D."""
+    return int(_lib.lib().blp_rank_relations_wide_workspace_bytes(_lib.MODEL_IDS[rel_model], int(D), int(Q), int(R)))
+
+
+def topk_relations_wide_supported(rel_model, dim, k):
+    """True if topk_relations_wide takes this width and k (rank_relations_wide's widths, 1 <= k <= 256)."""
+    return bool(_lib.lib().blp_topk_relations_wide_supported(_lib.MODEL_IDS[rel_model], int(dim), int(k)))
+
+
+def topk_relations_wide_workspace_bytes(rel_model, D, Q, R, k):
+    """Bytes of topk_relations_wide's workspace: 0 (the lists live on chip, every query has one owner)."""
+    return int(_lib.lib().blp_topk_relations_wide_workspace_bytes(_lib.MODEL_IDS[rel_model], int(D), int(Q), int(R), int(k)))
+
+
+def rank_relations_wide(rel_model, source, head_row, tail_row, rel_emb, true_rel=None, filter=None, return_scores=False, out=None):
+    """rank_relations for TransE at any width D % 4 == 0, 4 <= D <= 1024 (blp_rank_relations_wide: a lane holds 64 columns of
+    its relation row at a time and carries the running sums): the same arguments, the same counts and score bits."""
+    return _rank_relations(True, rel_model, source, head_row, tail_row, rel_emb, true_rel, filter, return_scores, out)
+
+
+def topk_relations_wide(rel_model, source, head_row, tail_row, rel_emb, k, filter=None, out=None):
+    """topk_relations for TransE at any width D % 4 == 0, 4 <= D <= 1024 (blp_topk_relations_wide): the same arguments, order,
+    padding and score bits."""
+    return _topk_relations(True, rel_model, source, head_row, tail_row, rel_emb, k, filter, out)
 
 
 def topk_merge(rows, scores, k):

@@ -960,16 +960,22 @@ def rank_relations(model, table, triples, ent2idx, *, filter_index=None, return_
     filter_index utils.RelationFilterIndex of the known edges: the other known relations of the pair leave the filtered counts
     Returns counts (T, 4) int32 = {gt, ge, gt_filt, ge_filt} -- relations scoring above / at least the true one, IEEE
     comparison, the true relation itself included in ge; metrics_from_counts applies unchanged -- and, with ``return_scores``,
-    the (T, R) score_fn values bit for bit.  HIP tensors at a width blp_rank_relations takes: the fused kernel (no (T, R)
-    matrix unless asked for); CPU tensors and other widths: score_fn broadcast over the relations in bounded pieces."""
+    the (T, R) score_fn values bit for bit.  HIP tensors at a width blp_rank_relations takes (64 / 128 / 256), or of a TransE
+    model at any width blp_rank_relations_wide takes (D % 4 == 0, 4 <= D <= 1024: the BOW / DKRL 300 and 768): the fused kernel
+    (no (T, R) matrix unless asked for); CPU tensors and everything else: score_fn broadcast over the relations in bounded
+    pieces.  The routes give the same bits."""
     model = _module(model)
     triples, head_rows, tail_rows, rel_w = _relation_queries(model, table, triples, ent2idx, "rank_relations", 3)
     device, T, R = table.device, triples.shape[0], rel_w.shape[0]
     filt = filter_index.segments(triples, device) if filter_index is not None and T else None
+    fused = None
     if table.is_cuda and ops.rank_relations_supported(model.rel_model, table.shape[1]):
+        fused = ops.rank_relations
+    elif table.is_cuda and ops.rank_relations_wide_supported(model.rel_model, table.shape[1]):
+        fused = ops.rank_relations_wide
+    if fused is not None:
         source, hr, tr = _relation_source(table, triples, ent2idx, head_rows, tail_rows)
-        return ops.rank_relations(model.rel_model, source, hr, tr, rel_w, triples[:, 2].contiguous(), filter=filt,
-                                  return_scores=return_scores)
+        return fused(model.rel_model, source, hr, tr, rel_w, triples[:, 2].contiguous(), filter=filt, return_scores=return_scores)
     counts = torch.empty((T, 4), dtype=torch.int32, device=device)
     scores = torch.empty((T, R), dtype=torch.float32, device=device) if return_scores else None
     dense_filt = None if filt is None else (filt.seg_lo, filt.seg_hi, filt.values, filt.exclude, None)
@@ -991,8 +997,8 @@ def predict_relations(model, table, pairs, k, ent2idx, *, filter_index=None):
     are REMOVED, except the row's third column when there is one (-1 there removes every known relation, as two columns do).
     Returns (rels (T, k) int64, scores (T, k) float32): descending score, ties by ascending relation id, NaN last; -1 / NaN
     beyond the relations left (k may exceed R).  Scores are score_fn's values bit for bit.  HIP tensors at a width
-    blp_topk_relations takes and k <= 256: the fused kernel; otherwise score_fn broadcast in bounded pieces + the stable
-    order (also the fused route's oracle)."""
+    blp_topk_relations takes -- or, a TransE model, blp_topk_relations_wide (D % 4 == 0, 4 <= D <= 1024) -- and k <= 256: the
+    fused kernel; otherwise score_fn broadcast in bounded pieces + the stable order (also the fused routes' oracle)."""
     model = _module(model)
     k = int(k)
     if k < 1:
@@ -1000,9 +1006,14 @@ def predict_relations(model, table, pairs, k, ent2idx, *, filter_index=None):
     pairs, head_rows, tail_rows, rel_w = _relation_queries(model, table, pairs, ent2idx, "predict_relations", 2)
     device, T, R = table.device, pairs.shape[0], rel_w.shape[0]
     filt = filter_index.segments(pairs, device) if filter_index is not None and T else None
+    fused = None
     if table.is_cuda and ops.topk_relations_supported(model.rel_model, table.shape[1], k):
+        fused = ops.topk_relations
+    elif table.is_cuda and ops.topk_relations_wide_supported(model.rel_model, table.shape[1], k):
+        fused = ops.topk_relations_wide
+    if fused is not None:
         source, hr, tr = _relation_source(table, pairs, ent2idx, head_rows, tail_rows)
-        return ops.topk_relations(model.rel_model, source, hr, tr, rel_w, k, filter=filt)
+        return fused(model.rel_model, source, hr, tr, rel_w, k, filter=filt)
     rels_out = torch.empty((T, k), dtype=torch.int64, device=device)
     scores_out = torch.empty((T, k), dtype=torch.float32, device=device)
     dense_filt = None if filt is None else (filt.seg_lo, filt.seg_hi, filt.values, filt.exclude, None)

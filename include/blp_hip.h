@@ -748,6 +748,38 @@ int blp_topk_relations(int model, const float *source, int64_t S, int D, int64_t
                        int64_t *rels, float *scores, void *workspace, size_t workspace_bytes, int device, void *stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Relation prediction for TransE at ANY width: blp_rank_relations_wide and blp_topk_relations_wide are blp_rank_relations and
+ * blp_topk_relations -- the same argument lists, the same outputs bit for bit (counts; scores with the reference's sign of
+ * zero; top-k order, padding, NaN as 0x7fc00000), the same filter rules, argument checks, error codes and order of checks --
+ * at the widths the BOW / DKRL encoders train TransE at (300: GloVe, 768: BERT embeddings), where a relation row no longer
+ * fits a lane's registers.  A caller switches by name.
+ * Limits: model BLP_MODEL_TRANSE only, D % 4 == 0 and 4 <= D <= 1024 (blp_rank_relations_wide_supported; the top-k call also
+ *   1 <= k <= 256); any other model or width: BLP_ERR_UNSUPPORTED_DIM.  64 / 128 / 256 are inside the rule: there the two
+ *   pairs of calls give identical results.  Everything else as above: 1 <= R < 2^31; Q <= 2^30; Q x k < 2^31; source /
+ *   rel_emb / outputs 16-byte aligned, ld_src % 4 == 0, ld_src >= D; Q = 0 succeeds and touches nothing; every check runs
+ *   before a device is touched.
+ * Workspace, 256-B aligned: blp_rank_relations_wide_workspace_bytes = 4 Q bytes rounded up to 256 (the true relations'
+ *   scores; used with counts only), whatever R and D; blp_topk_relations_wide_workspace_bytes = 0 (one owning workgroup per
+ *   query, its k-lists in on-chip memory; the winners' scores are written from the selection keys, which carry them exactly).
+ * TransE's sum runs strictly left to right, so the kernels carry one running sum per (relation, query) across 64-column slabs
+ * of the relation row: the value after the last column is score_fn's, bit for bit, at every width.
+ * Asynchronous on `stream`, no host synchronisation, no allocation.  Deterministic; nothing depends on the grid.
+ * (Added after 6.0.0 without a version change: no existing entry point changed.)
+ * -------------------------------------------------------------------------------------------- */
+int blp_rank_relations_wide_supported(int model, int D);
+size_t blp_rank_relations_wide_workspace_bytes(int model, int D, int64_t Q, int64_t R);
+int blp_rank_relations_wide(int model, const float *source, int64_t S, int D, int64_t ld_src, const int64_t *head_row,
+                            const int64_t *tail_row, int64_t Q, const float *rel_emb, int64_t R, const int64_t *true_rel,
+                            const blp_filter *filter, int32_t *counts, float *scores, int64_t ld_scores, void *workspace,
+                            size_t workspace_bytes, int device, void *stream);
+int blp_topk_relations_wide_supported(int model, int D, int k);
+size_t blp_topk_relations_wide_workspace_bytes(int model, int D, int64_t Q, int64_t R, int k);
+int blp_topk_relations_wide(int model, const float *source, int64_t S, int D, int64_t ld_src, const int64_t *head_row,
+                            const int64_t *tail_row, int64_t Q, const float *rel_emb, int64_t R, int k,
+                            const blp_filter *filter, int64_t *rels, float *scores, void *workspace, size_t workspace_bytes,
+                            int device, void *stream);
+
+/* --------------------------------------------------------------------------------------------
  * Re-ranking a first-stage retrieval run (reference retrieval.py rerank: BM25F candidates of DBpedia-Entity v2 re-scored
  * with entity embeddings, the mixing weight alpha chosen per fold by nDCG@100).  Candidates are a CSR over Q queries:
  * query q owns candidates [cand_ptr[q], cand_ptr[q + 1]) (cand_ptr (Q + 1) int64, cand_ptr[0] = 0, cand_ptr[Q] = C).

@@ -10,9 +10,15 @@ lane-op roof (78.6 T lane-ops/s) at 3 lane-ops per (pair, column) -- TransE: add
 multiply, add.
 
     python tools/rank_relations_bench.py [--steps 30] [--warmup 3] [--repeats 5] [--only NAME ...] [--out FILE.jsonl]
+                                         [--width D ...]
 
   fb15k237-{transe,distmult}     310 116 pairs over a 14 541 x 128 table, R = 237
   wikidata5m-{transe,distmult}   1 000 000 pairs over 100 000 x 128 gathered rows, R = 822
+
+--width D ... : instead of the four workloads above, fb15k237-transe at each width D through the any-width calls
+(blp_rank_relations_wide / blp_topk_relations_wide; the BOW / DKRL encoders train TransE at 300 and 768), as workload
+fb15k237-transe-wide<D>, against the same yardstick.  At a width the register kernels take as well (64 / 128 / 256) they join the
+alternation (register_counts / register_topk) and the line carries the wide call's time over theirs: the cost of the slab form.
 """
 import argparse
 import json
@@ -59,7 +65,7 @@ def summary(medians):
     return {"median_ms": round(mid, 4), "spread": round(float((a.max() - a.min()) / mid), 4), "medians_ms": [round(float(x), 4) for x in a]}
 
 
-def run(name, cfg, steps, warmup, repeats):
+def run(name, cfg, steps, warmup, repeats, wide=False):
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(0)
     S, D, Q, R, model = cfg["S"], cfg["D"], cfg["Q"], cfg["R"], cfg["model"]
@@ -78,12 +84,13 @@ def run(name, cfg, steps, warmup, repeats):
     rels = rel_w.unsqueeze(0)
     owner = torch.arange(Q, device=dev).repeat_interleave(2)
     res = {}
+    rank_fn, topk_fn = (ops.rank_relations_wide, ops.topk_relations_wide) if wide else (ops.rank_relations, ops.topk_relations)
 
     def matrix(a, b):
         return ops.score(model, source[hr[a:b]].unsqueeze(1), source[tr[a:b]].unsqueeze(1), rels)
 
     def fused_counts():
-        res["fc"] = ops.rank_relations(model, source, hr, tr, rel_w, true, filter=filt)
+        res["fc"] = rank_fn(model, source, hr, tr, rel_w, true, filter=filt)
 
     def yard_counts():
         out = torch.empty((Q, 4), dtype=torch.int32, device=dev)
@@ -93,7 +100,7 @@ def run(name, cfg, steps, warmup, repeats):
         res["yc"] = out
 
     def fused_topk():
-        res["ft"] = ops.topk_relations(model, source, hr, tr, rel_w, K, filter=filt)
+        res["ft"] = topk_fn(model, source, hr, tr, rel_w, K, filter=filt)
 
     def yard_topk():
         ids = torch.empty((Q, K), dtype=torch.int64, device=dev)
@@ -111,16 +118,32 @@ def run(name, cfg, steps, warmup, repeats):
     torch.cuda.synchronize()
     counts_equal = bool(torch.equal(res["fc"], res["yc"]))
     topk_equal = bool(torch.equal(res["ft"][0], res["yt"][0]) and torch.equal(res["ft"][1].view(torch.int32), res["yt"][1].view(torch.int32)))
-    runs = [measure({"fused_counts": fused_counts, "yard_counts": yard_counts, "fused_topk": fused_topk, "yard_topk": yard_topk}, steps, warmup)
-            for _ in range(repeats)]
+    calls = {"fused_counts": fused_counts, "yard_counts": yard_counts, "fused_topk": fused_topk, "yard_topk": yard_topk}
+    extra = {}
+    if wide and ops.rank_relations_supported(model, D):  # the register kernels on the same inputs, in the same alternation
+        def register_counts():
+            res["rc"] = ops.rank_relations(model, source, hr, tr, rel_w, true, filter=filt)
+
+        def register_topk():
+            res["rt"] = ops.topk_relations(model, source, hr, tr, rel_w, K, filter=filt)
+        register_counts(), register_topk()
+        torch.cuda.synchronize()
+        extra["counts_equal_register"] = bool(torch.equal(res["fc"], res["rc"]))
+        extra["topk_equal_register"] = bool(torch.equal(res["ft"][0], res["rt"][0]) and
+                                            torch.equal(res["ft"][1].view(torch.int32), res["rt"][1].view(torch.int32)))
+        calls.update(register_counts=register_counts, register_topk=register_topk)
+    runs = [measure(calls, steps, warmup) for _ in range(repeats)]
     s = {n: summary([r[n] for r in runs]) for n in runs[0]}
     lane_ops = Q * R * D * OPS_PER_COLUMN
     roof = lambda n: round(lane_ops / (s[n]["median_ms"] * 1e-3) / ROOF_LANE_OPS, 4)
+    if "register_counts" in s:
+        extra["counts_wide_over_register"] = round(s["fused_counts"]["median_ms"] / s["register_counts"]["median_ms"], 2)
+        extra["topk_wide_over_register"] = round(s["fused_topk"]["median_ms"] / s["register_topk"]["median_ms"], 2)
     return {"workload": name, **cfg, "k": K, "filter_entries_per_query": 2, "steps": steps, "warmup": warmup, "repeats": repeats,
             "counts_equal_yardstick": counts_equal, "topk_equal_yardstick": topk_equal, **s,
             "counts_yardstick_over_fused": round(s["yard_counts"]["median_ms"] / s["fused_counts"]["median_ms"], 2),
             "topk_yardstick_over_fused": round(s["yard_topk"]["median_ms"] / s["fused_topk"]["median_ms"], 2),
-            "counts_roof_fraction": roof("fused_counts"), "topk_roof_fraction": roof("fused_topk")}
+            "counts_roof_fraction": roof("fused_counts"), "topk_roof_fraction": roof("fused_topk"), **extra}
 
 
 def main():
@@ -130,11 +153,15 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--only", nargs="*")
     ap.add_argument("--out")
+    ap.add_argument("--width", type=int, nargs="*", help="fb15k237-transe at these widths through the any-width calls")
     args = ap.parse_args()
-    for name, cfg in WORKLOADS.items():
+    workloads = WORKLOADS
+    if args.width:
+        workloads = {f"fb15k237-transe-wide{D}": dict(WORKLOADS["fb15k237-transe"], D=D) for D in args.width}
+    for name, cfg in workloads.items():
         if args.only and name not in args.only:
             continue
-        line = json.dumps(run(name, cfg, args.steps, args.warmup, args.repeats))
+        line = json.dumps(run(name, cfg, args.steps, args.warmup, args.repeats, wide=bool(args.width)))
         print(line, flush=True)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
