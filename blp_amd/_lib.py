@@ -31,6 +31,7 @@ SYMBOLS = ("blp_version", "blp_last_error", "blp_device_caps", "blp_selftest", "
            "blp_rank_lists_supported", "blp_rank_lists_workspace_bytes", "blp_rank_lists",
            "blp_rank_sets_supported", "blp_rank_sets_workspace_bytes", "blp_rank_sets",
            "blp_rank_sets_typed_supported", "blp_rank_sets_typed_workspace_bytes", "blp_rank_sets_typed",
+           "blp_rank_sets_wide_supported", "blp_rank_sets_wide_workspace_bytes", "blp_rank_sets_wide",
            "blp_topk_sets_supported", "blp_topk_sets_workspace_bytes", "blp_topk_sets",
            "blp_topk_sets_typed_supported", "blp_topk_sets_typed_workspace_bytes", "blp_topk_sets_typed",
            "blp_topk_lists_supported", "blp_topk_lists_workspace_bytes", "blp_topk_lists",
@@ -238,6 +239,10 @@ def _load(path, hooks):
     L.blp_rank_sets_typed.restype = _i
     L.blp_rank_sets_typed.argtypes = [_i, _vp, _i, _i64, _i, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp,
                                       _i64, _i64, _vp, _vp, ctypes.POINTER(BlpFilter), _vp, _vp, _sz, _i, _vp]
+    for wide, typed in ((L.blp_rank_sets_wide_supported, L.blp_rank_sets_typed_supported),
+                        (L.blp_rank_sets_wide_workspace_bytes, L.blp_rank_sets_typed_workspace_bytes),
+                        (L.blp_rank_sets_wide, L.blp_rank_sets_typed)):  # blp_rank_sets_typed's signatures, by design
+        wide.restype, wide.argtypes = typed.restype, list(typed.argtypes)
     L.blp_topk_sets_supported.restype = _i
     L.blp_topk_sets_supported.argtypes = [_i, _i, _i]
     L.blp_topk_sets_workspace_bytes.restype = _sz

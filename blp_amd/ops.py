@@ -6,6 +6,7 @@ device memory and the stream; every arithmetic step of the hot path runs in the 
     topk(...)           filtered top-k prediction per query (no score matrix)
     rank_lists(...)     counts / scores of per-query candidate lists (only the listed rows are read)
     rank_sets(...)      counts against candidate sets shared by groups of queries (type-constrained evaluation)
+    rank_sets_wide(...) the same for TransE at any width D % 4 == 0, 4 <= D <= 1024 (the BOW / DKRL 300 and 768)
     topk_sets(...)      filtered top-k prediction inside candidate sets shared by groups of queries
     rerank_cosine(...)  cosine of every retrieval candidate with its query (retrieval.py:170-175)
     rerank_ndcg(...)    trec_eval ndcg_cut of every (alpha, query) of a re-ranked run (retrieval.py:139-258)
@@ -517,9 +518,43 @@ def rank_sets(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, tru
     global rows [row_base, row_base + N) --, strictly ascending within a set; entries outside the shard are skipped.
     Returns counts (Q, 4) int32 {gt, ge, gt_filtered, ge_filtered} over the entries of each query's set (``filter``: a
     SegmentFilter whose row_base is ``row_base``; an entry of it counts only if its row is in the set)."""
+    return _rank_sets(False, rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, true_row, set_ptr, set_row, qset_ptr_head,
+                      qset_ptr_tail, filter, row_base, out)
+
+
+def rank_sets_wide_supported(rel_model, dim, dtype=torch.float32):
+    """True if rank_sets_wide takes this width and table dtype (blp_rank_sets_wide_supported: transe, D % 4 == 0, 4 <= D <= 1024 --
+    the BOW / DKRL encoders' 300 and 768; a float32, float16 or bfloat16 table)."""
+    if dtype not in TABLE_DTYPES:
+        return False
+    return bool(_lib.lib().blp_rank_sets_wide_supported(_lib.MODEL_IDS[rel_model], TABLE_DTYPES[dtype], int(dim)))
+
+
+def rank_sets_wide_workspace_bytes(rel_model, D, q_head, q_tail, num_sets, dtype=torch.float32):
+    """Bytes of rank_sets_wide's workspace: true keys, accumulators, coefficient rows and num_sets + 1 unit offsets, whatever
+    the table's length and the sets' sizes (0: not supported, or a negative size)."""
+    if dtype not in TABLE_DTYPES:
+        return 0
+    return int(_lib.lib().blp_rank_sets_wide_workspace_bytes(_lib.MODEL_IDS[rel_model], TABLE_DTYPES[dtype], int(D), int(q_head),
+                                                            int(q_tail), int(num_sets)))
+
+
+def rank_sets_wide(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, true_row, set_ptr, set_row, qset_ptr_head,
+                   qset_ptr_tail, filter=None, row_base=0, out=None):
+    """rank_sets for TransE at any width D % 4 == 0, 4 <= D <= 1024 (blp_rank_sets_wide: a lane holds 64 columns of its set row at
+    a time and the running sums of a chunk of 16 queries of the set's group): same arguments, same counts -- the reference's bit
+    for bit, on a 16-bit table those of the table widened to float32."""
+    return _rank_sets(True, rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, true_row, set_ptr, set_row, qset_ptr_head,
+                      qset_ptr_tail, filter, row_base, out)
+
+
+def _rank_sets(wide, rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, true_row, set_ptr, set_row, qset_ptr_head,
+               qset_ptr_tail, filter, row_base, out):
+    """rank_sets (blp_rank_sets_typed) and rank_sets_wide (blp_rank_sets_wide): one argument handling, two entries."""
+    who = "rank_sets_wide" if wide else "rank_sets"
     _require_device(table, source, fixed_row, rel_emb, rel_ids, true_row, set_ptr, set_row, qset_ptr_head, qset_ptr_tail)
     if table.dtype not in TABLE_DTYPES:
-        raise TypeError(f"rank_sets reads a float32, float16 or bfloat16 table, got {table.dtype}")
+        raise TypeError(f"{who} reads a float32, float16 or bfloat16 table, got {table.dtype}")
     if source is table and table.dtype != torch.float32:
         raise TypeError("a 16-bit table needs a float32 `source` for the queries' vectors")
     same = source is table
@@ -539,10 +574,12 @@ def rank_sets(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, tru
         raise ValueError("set_ptr, qset_ptr_head and qset_ptr_tail need G + 1 entries each")
     if not 0 <= q_head <= Q:
         raise ValueError(f"q_head = {q_head} outside [0, {Q}]")
-    if not rank_sets_supported(rel_model, D, table.dtype):
+    if wide and not rank_sets_wide_supported(rel_model, D, table.dtype):
+        raise ValueError(f"rank_sets_wide: {rel_model} at D = {D} not supported (transe, D % 4 == 0, 4 <= D <= 1024: see rank_sets_wide_supported)")
+    if not wide and not rank_sets_supported(rel_model, D, table.dtype):
         raise ValueError(f"rank_sets: D = {D} not supported (64 / 128 / 256: see rank_sets_supported)")
     if filter is not None and int(filter.row_base) != int(row_base):
-        raise ValueError(f"rank_sets: the filter's row_base {filter.row_base} differs from row_base {row_base}")
+        raise ValueError(f"{who}: the filter's row_base {filter.row_base} differs from row_base {row_base}")
     dev = table.device
     counts = torch.empty((Q, 4), dtype=torch.int32, device=dev) if out is None else out
     if counts.shape != (Q, 4) or counts.dtype != torch.int32 or not counts.is_contiguous():
@@ -553,17 +590,17 @@ def rank_sets(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, tru
     model = _lib.MODEL_IDS[rel_model]
     stream = torch._C._cuda_getCurrentRawStream(dev.index)
     tdt = TABLE_DTYPES[table.dtype]
-    ws_bytes = L.blp_rank_sets_typed_workspace_bytes(model, tdt, D, q_head, Q - q_head, G)
+    ws_bytes = (L.blp_rank_sets_wide_workspace_bytes if wide else L.blp_rank_sets_typed_workspace_bytes)(model, tdt, D, q_head, Q - q_head, G)
     workspace = _workspace(dev, stream, ws_bytes)
     spec = None if filter is None else _filter_spec(filter, Q, dev)
-    status = L.blp_rank_sets_typed(model, table.data_ptr(), tdt, N, D, table.stride(0) if tdt or N > 1 else D, int(row_base),
+    status = (L.blp_rank_sets_wide if wide else L.blp_rank_sets_typed)(model, table.data_ptr(), tdt, N, D, table.stride(0) if tdt or N > 1 else D, int(row_base),
                                    source.data_ptr(), source.shape[0], source.stride(0) if source.shape[0] > 1 else D,
                                    fixed_row.data_ptr(), rel_emb.data_ptr(), rel_emb.shape[0], rel_ids.data_ptr(), true_row.data_ptr(),
                                    q_head, Q - q_head, set_ptr.data_ptr(), _addr(set_row) if nnz else None, nnz, G,
                                    qset_ptr_head.data_ptr(), qset_ptr_tail.data_ptr(), spec, counts.data_ptr(), workspace.data_ptr(),
                                    ws_bytes, dev.index, stream)
     if status:
-        _lib.check(status, "blp_rank_sets_typed" if tdt else "blp_rank_sets")
+        _lib.check(status, "blp_rank_sets_wide" if wide else "blp_rank_sets_typed" if tdt else "blp_rank_sets")
     return counts
 
 

@@ -1201,7 +1201,10 @@ def rank_in_sets(model, table, triples, sets, ent2idx, *, set_ids=None, side="bo
     Returns counts (Q, 4) int32 {gt, ge, gt_filtered, ge_filtered} in the caller's order.
     A float32, float16 or bfloat16 HIP table at 64 / 128 / 256 goes through blp_rank_sets / blp_rank_sets_typed (every row of a
     set is fetched once per chunk of 128 queries of its group; a 16-bit table is read as it is, only the Q fixed and the Q true
-    rows are gathered and widened); CPU tensors and other widths take the dense route: score_fn on gathered rows."""
+    rows are gathered and widened).  A HIP table at any other width blp_rank_sets_wide takes -- TransE, D % 4 == 0, 4 <= D <= 1024:
+    the BOW / DKRL 300 and 768 -- goes through blp_rank_sets_wide (a row of a set fetched once per chunk of 16 queries of its
+    group; the same counts, a 16-bit table handled the same way).  CPU tensors, and the bilinear models at other widths, take the
+    dense route: score_fn on gathered rows."""
     model = _module(model)
     if side not in ("head", "tail", "both"):
         raise ValueError(f"side must be 'head', 'tail' or 'both', got {side!r}")
@@ -1248,7 +1251,12 @@ def rank_in_sets(model, table, triples, sets, ent2idx, *, set_ids=None, side="bo
                                  seg.exclude[sel].contiguous(), seg.ent2idx, 0)
     if Q == 0:
         return torch.empty((0, 4), dtype=torch.int32, device=device)
+    fused = None
     if table.is_cuda and ops.rank_sets_supported(model.rel_model, D, table.dtype):
+        fused = ops.rank_sets
+    elif table.is_cuda and ops.rank_sets_wide_supported(model.rel_model, D, table.dtype):
+        fused = ops.rank_sets_wide
+    if fused is not None:
         if table.dtype != torch.float32:
             # float32 query vectors: the Q fixed rows, then the Q true rows, gathered and widened (exact) by the library's own
             # kernel (blp_gather_triple_vectors: 64-bit offsets, a table of more than 2^31 bytes included)
@@ -1257,8 +1265,8 @@ def rank_in_sets(model, table, triples, sets, ent2idx, *, set_ids=None, side="bo
             src_fixed, src_true = torch.arange(Q, device=device), torch.arange(Q, 2 * Q, device=device)
         else:
             source, src_fixed, src_true = table, g_fixed, g_true
-        grouped = ops.rank_sets(model.rel_model, table, source, src_fixed, rel_w, g_rel, q_head, src_true, set_ptr, set_rows, qptr_head,
-                                qptr_tail, filter=filt)
+        grouped = fused(model.rel_model, table, source, src_fixed, rel_w, g_rel, q_head, src_true, set_ptr, set_rows, qptr_head, qptr_tail,
+                        filter=filt)
     else:
         dense_filt = None if filt is None else (filt.seg_lo, filt.seg_hi, filt.values, filt.exclude, filt.ent2idx)
         grouped = _rank_sets_dense(model.score_fn, table, table[g_fixed].float(), rel_w[g_rel], table[g_true].float(), q_head,

@@ -596,6 +596,33 @@ int blp_rank_sets_typed(int model, const void *table, int table_dtype, int64_t N
                         const int64_t *set_row, int64_t nnz, int64_t G, const int64_t *qset_ptr_head,
                         const int64_t *qset_ptr_tail, const blp_filter *filter, int32_t *counts, void *workspace,
                         size_t workspace_bytes, int device, void *stream);
+/* Candidate sets shared between queries for TransE at ANY width: blp_rank_sets_wide is blp_rank_sets_typed -- the contract
+ * above word for word: the sets CSR of strictly ascending global rows, row_base shards with entries outside [row_base,
+ * row_base + N) skipped, the grouping by qset_ptr_head / qset_ptr_tail, the filter (an entry is subtracted only if its row is
+ * in the query's set; the triple's own entity is never removed), the true entity (adds to ge iff its row is in the set), the
+ * (Q, 4) int32 counts in grouped order, the reference's bit for bit (a 16-bit table: of the table widened to f32) -- at the
+ * widths blp_rank_sets_supported refuses: the BOW / DKRL encoders' 300 and 768.  A lane holds 64 columns of its set row at a
+ * time and the running sums of a chunk of 16 queries of the set's group (rank_sets_wide.hip): a row of a set is fetched once
+ * per (set, chunk of 16 queries of its group).
+ * Limits (blp_rank_sets_wide_supported): BLP_MODEL_TRANSE only, table_dtype a BLP_DTYPE_*, D % 4 == 0 and 4 <= D <= 1024 --
+ * 64 / 128 / 256 included, where it is a second implementation of the same bits (blp_rank_sets is the faster one); the other
+ * models, other widths and unknown dtypes answer 0.  Q <= 2^30; nnz < 2^31; row_base + N <= 2^31; table / source / rel_emb /
+ * counts 16-byte aligned, ld % 4 == 0 (f32) or ld % 8 == 0 (a 16-bit table, in elements), ld_src % 4 == 0.  Status codes and
+ * messages as blp_rank_sets_typed.
+ * Workspace: blp_rank_sets_wide_workspace_bytes(model, table_dtype, D, q_head, q_tail, G) bytes (0 where unsupported or a
+ * size is negative), 256-B aligned: true keys (4 Q bytes), accumulators (8 Q), per-query coefficient rows (2 D floats per
+ * head-replacing query, D per tail-replacing one) and G + 1 int64 of work-unit offsets -- independent of N and nnz.
+ * Asynchronous on `stream`, no host synchronisation, no allocation; nothing about set or group sizes is read on the host.
+ * Deterministic: partial counts are combined by integer adds, so nothing depends on the grid.
+ * (Added after 6.0.0 without a version change: no existing entry point changed.) */
+int blp_rank_sets_wide_supported(int model, int table_dtype, int D);
+size_t blp_rank_sets_wide_workspace_bytes(int model, int table_dtype, int D, int64_t q_head, int64_t q_tail, int64_t G);
+int blp_rank_sets_wide(int model, const void *table, int table_dtype, int64_t N, int D, int64_t ld, int64_t row_base,
+                       const float *source, int64_t S, int64_t ld_src, const int64_t *fixed_row, const float *rel_emb, int64_t R,
+                       const int64_t *rel_id, const int64_t *true_row, int64_t q_head, int64_t q_tail, const int64_t *set_ptr,
+                       const int64_t *set_row, int64_t nnz, int64_t G, const int64_t *qset_ptr_head,
+                       const int64_t *qset_ptr_tail, const blp_filter *filter, int32_t *counts, void *workspace,
+                       size_t workspace_bytes, int device, void *stream);
 
 /* --------------------------------------------------------------------------------------------
  * Filtered top-k INSIDE candidate sets shared between queries: ANSWER a query (h, r, ?) / (?, r, t) with the k rows of ITS SET

@@ -8,10 +8,17 @@ then --steps steps; one JSON line with the median and p90 of both, their ratio a
 call (rows fetched: one per set entry and chunk of 128 queries of its group, D x 4 bytes each).
 
     python tools/rank_sets_bench.py [--steps 30] [--warmup 3] [--only NAME ...] [--out FILE.jsonl] [--table16 {f16,bf16}]
+                                    [--width D [D ...]] [--repeats 5]
 
 --table16: the table rounded to IEEE half / bfloat16 instead; blp_rank_sets_typed on the 16-bit table alternates with
 blp_rank_sets on that table widened to f32 (the yardstick), counts required equal first; one JSON line with both medians,
 their ratio (16-bit over f32) and the gather bandwidth of the 16-bit call (D x 2 bytes per fetched row).
+
+--width D [D ...] (combinable with --table16): blp_rank_sets_wide -- TransE at any width -- on the fb15k237-transe shape at
+width D (105 740 queries, 474 sets, 14 541 rows).  At the widths blp_rank_sets takes (64 / 128 / 256) it alternates with
+blp_rank_sets, elsewhere (300, 768) with blp_rank_lists on the expanded lists; counts required equal first; --repeats
+measurements of --steps steps each, one JSON line with the median of the medians of both routes, their ratio and the spread of
+the repeated medians ((max - min) / median).
 
   fb15k237-{transe,distmult}   105 740 queries, 14 541 x 128 table, 474 sets of 50 .. 8 000 rows (log-uniform)
   longtable-transe             13 788 queries, 4.6 M x 128 table, 1 644 sets of 10^3 .. 10^6 rows (log-uniform)
@@ -58,7 +65,8 @@ def stats(ms):
     return {"median": round(float(np.median(a)), 4), "p90": round(float(np.percentile(a, 90)), 4)}
 
 
-def run(name, cfg, steps, warmup, table16=None):
+def make_workload(cfg):
+    """The table, relations, sets, grouped queries and filter of a workload, on the device."""
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(0)
     rng = np.random.default_rng(0)
@@ -94,15 +102,14 @@ def run(name, cfg, steps, warmup, table16=None):
     lo = torch.arange(Q, device=dev) * FILTER_PER_QUERY
     filt = ops.SegmentFilter(lo, lo + FILTER_PER_QUERY, seg.reshape(-1).contiguous(), None, None, 0)
     counts = torch.empty((Q, 4), dtype=torch.int32, device=dev)
-    if table16:  # (the f32 original is not kept: the 16-bit copy and its widened image replace it)
-        small = table.to({"f16": torch.float16, "bf16": torch.bfloat16}[table16])
-        del table
-        return run16(name, cfg, steps, warmup, table16, small, rel_w, fixed, true, rel_ids, q_head, set_ptr, set_row, qh, qt, filt, counts)
+    return dict(table=table, rel_w=rel_w, set_ptr=set_ptr, set_row=set_row, q_head=q_head, qh=qh, qt=qt, fixed=fixed, true=true,
+                rel_ids=rel_ids, n_per=n_per, first=first, filt=filt, counts=counts)
 
-    def fused():
-        ops.rank_sets(cfg["model"], table, table, fixed, rel_w, rel_ids, q_head, true, set_ptr, set_row, qh, qt, filter=filt, out=counts)
 
-    # the expanded route: per-query lists, in calls of at most MAX_LIST_ENTRIES entries, each of one side
+def expanded_calls(w, Q):
+    """The sets expanded into per-query lists, in calls of at most MAX_LIST_ENTRIES entries, each of one side:
+    [(a, b, list_ptr, list_row, filter)] and the number of (query, row) pairs."""
+    dev, n_per, q_head, filt = w["table"].device, w["n_per"], w["q_head"], w["filt"]
     list_ptr_all = torch.zeros(Q + 1, dtype=torch.long, device=dev)
     list_ptr_all[1:] = torch.cumsum(n_per, 0)
     host_ptr = list_ptr_all.tolist()
@@ -114,11 +121,30 @@ def run(name, cfg, steps, warmup, table16=None):
             b += 1
         n = host_ptr[b] - host_ptr[a]
         owner = torch.repeat_interleave(torch.arange(a, b, device=dev), n_per[a:b], output_size=n)
-        rows = set_row[first[owner] + torch.arange(host_ptr[a], host_ptr[b], device=dev) - list_ptr_all[owner]]
+        rows = w["set_row"][w["first"][owner] + torch.arange(host_ptr[a], host_ptr[b], device=dev) - list_ptr_all[owner]]
         del owner
         part = ops.SegmentFilter(filt.seg_lo[a:b].contiguous(), filt.seg_hi[a:b].contiguous(), filt.values, None, None, 0)
         calls.append((a, b, (list_ptr_all[a:b + 1] - host_ptr[a]).contiguous(), rows, part))
         a = b
+    return calls, host_ptr[Q]
+
+
+def run(name, cfg, steps, warmup, table16=None):
+    w = make_workload(cfg)
+    N, D, Q, G = cfg["N"], cfg["D"], cfg["Q"], cfg["G"]
+    table, rel_w, set_ptr, set_row, q_head, qh, qt = (w[k] for k in ("table", "rel_w", "set_ptr", "set_row", "q_head", "qh", "qt"))
+    fixed, true, rel_ids, n_per, filt, counts = (w[k] for k in ("fixed", "true", "rel_ids", "n_per", "filt", "counts"))
+    dev = table.device
+    if table16:  # (the f32 original is not kept: the 16-bit copy and its widened image replace it)
+        small = table.to({"f16": torch.float16, "bf16": torch.bfloat16}[table16])
+        del table
+        w.clear()
+        return run16(name, cfg, steps, warmup, table16, small, rel_w, fixed, true, rel_ids, q_head, set_ptr, set_row, qh, qt, filt, counts)
+
+    def fused():
+        ops.rank_sets(cfg["model"], table, table, fixed, rel_w, rel_ids, q_head, true, set_ptr, set_row, qh, qt, filter=filt, out=counts)
+
+    calls, _ = expanded_calls(w, Q)  # outside the timing
     expanded_counts = torch.empty((Q, 4), dtype=torch.int32, device=dev)
 
     def expanded():
@@ -176,6 +202,67 @@ def run16(name, cfg, steps, warmup, table16, small, rel_w, fixed, true, rel_ids,
             "gather_TBps_f32": round(fetched_rows * D * 4 / (a["median"] * 1e-3) / 1e12, 3), "steps": steps}
 
 
+def repeated(runs, name):
+    a = np.asarray([float(np.median(r[name])) for r in runs])
+    mid = float(np.median(a))
+    return {"median_ms": round(mid, 4), "spread": round(float((a.max() - a.min()) / mid), 4), "medians_ms": [round(float(x), 4) for x in a]}
+
+
+def run_wide(D, steps, warmup, repeats, table16=None):
+    """blp_rank_sets_wide at width D on the fb15k237-transe shape, next to blp_rank_sets (64 / 128 / 256) or to blp_rank_lists
+    on the expanded lists (any other width)."""
+    cfg = dict(WORKLOADS["fb15k237-transe"], D=int(D))
+    w = make_workload(cfg)
+    Q = cfg["Q"]
+    table, source, fixed, true = w["table"], w["table"], w["fixed"], w["true"]
+    if table16:  # the 16-bit table as it is; the queries' f32 vectors gathered and widened, as ranking.rank_in_sets does
+        table = table.to({"f16": torch.float16, "bf16": torch.bfloat16}[table16])
+        source = ops.gather_triple_vectors(torch.stack((fixed, true, torch.zeros_like(fixed)), dim=1), None, table)
+        fixed, true = torch.arange(Q, device=table.device), torch.arange(Q, 2 * Q, device=table.device)
+    sets_args = (w["rel_w"], w["rel_ids"], w["q_head"], true, w["set_ptr"], w["set_row"], w["qh"], w["qt"])
+    counts, other_counts = w["counts"], torch.empty_like(w["counts"])
+
+    def wide():
+        ops.rank_sets_wide("transe", table, source, fixed, *sets_args, filter=w["filt"], out=counts)
+
+    pairs = int(w["n_per"].sum())
+    if ops.rank_sets_supported("transe", D, table.dtype):
+        other_name = "rank_sets"
+
+        def other():
+            ops.rank_sets("transe", table, source, fixed, *sets_args, filter=w["filt"], out=other_counts)
+    else:
+        other_name = "expanded_lists"
+        calls, _ = expanded_calls(w, Q)  # outside the timing
+
+        def other():
+            for a, b, ptr, rows, part in calls:
+                ops.rank_lists("transe", table, source, fixed[a:b], w["rel_w"], w["rel_ids"][a:b], min(max(w["q_head"] - a, 0), b - a), ptr,
+                               rows, true_row=true[a:b], filter=part, out=(other_counts[a:b], None))
+
+    wide()
+    other()
+    same = bool(torch.equal(counts, other_counts))
+    head = {"workload": f"fb15k237-transe-wide-{D}", **cfg, "table16": table16, "against": other_name, "counts_equal": same}
+    if not same:
+        return head
+    runs = [measure({"wide": wide, "other": other}, steps, warmup) for _ in range(repeats)]
+    a, b = repeated(runs, "wide"), repeated(runs, "other")
+    return {**head, "set_entries": int(w["set_row"].numel()), "pairs": pairs, "filter_entries_per_query": FILTER_PER_QUERY,
+            "sets_wide_ms": a, f"{other_name}_ms": b, f"{other_name}_over_sets_wide": round(b["median_ms"] / a["median_ms"], 3),
+            "pairs_per_s": round(pairs / (a["median_ms"] * 1e-3), 0), "steps": steps, "warmup": warmup, "repeats": repeats}
+
+
+def emit(line, out):
+    print(line, flush=True)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "a") as fh:
+            fh.write(line + "\n")
+    ops.release_workspaces()
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
@@ -183,18 +270,17 @@ def main():
     ap.add_argument("--only", nargs="*")
     ap.add_argument("--out")
     ap.add_argument("--table16", choices=("f16", "bf16"))
+    ap.add_argument("--width", type=int, nargs="+", help="blp_rank_sets_wide at these widths on the fb15k237-transe shape")
+    ap.add_argument("--repeats", type=int, default=5, help="with --width: measurements whose medians' spread is reported")
     args = ap.parse_args()
+    for D in args.width or ():
+        emit(json.dumps(run_wide(D, args.steps, args.warmup, args.repeats, args.table16)), args.out)
+    if args.width:
+        return
     for name, cfg in WORKLOADS.items():
         if args.only and name not in args.only:
             continue
-        line = json.dumps(run(name, cfg, args.steps, args.warmup, args.table16))
-        print(line, flush=True)
-        if args.out:
-            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-            with open(args.out, "a") as fh:
-                fh.write(line + "\n")
-        ops.release_workspaces()
-        torch.cuda.empty_cache()
+        emit(json.dumps(run(name, cfg, args.steps, args.warmup, args.table16)), args.out)
 
 
 if __name__ == "__main__":
