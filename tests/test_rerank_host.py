@@ -1,5 +1,6 @@
 """retrieval.py rerank without a GPU: the parsers, trec_eval's ndcg_cut as blp_amd.retrieval restates it (the worked example
-and the edge cases of the contract), the alpha selection rules, the C entry points' argument refusals (before any device is
+and the edge cases of the contract), both restatements against plain references at the numeric and tie edges (the inputs
+tests/test_gpu_rerank_edges.py runs on the device), the alpha selection rules, the C entry points' argument refusals (before any device is
 touched), and the CLI end to end on a synthetic corpus against an independent restatement of the reference's loop."""
 import ctypes
 import json
@@ -178,6 +179,298 @@ def test_trec_ndcg_cut_matches_pytrec_eval():
     got = pytrec_eval.RelevanceEvaluator(qrels, {"ndcg_cut_10", "ndcg_cut_100"}).evaluate(run)
     for i, q in enumerate(p.query_ids):
         assert abs(got[q]["ndcg_cut_10"] - nd[0, i, 0]) < 1e-12 and abs(got[q]["ndcg_cut_100"] - nd[0, i, 1]) < 1e-12
+
+
+# ------------------------------------------------------------------------------------------------ plain references and edges
+# The inputs below are built here, on the host, and tests/test_gpu_rerank_edges.py runs the kernels on exactly these.  The
+# references use neither blp_amd.retrieval nor the device: Python floats and numpy float32 scalars, one candidate at a time.
+F32_TINY = np.finfo(np.float32).tiny  # the smallest normal float32
+CLAMP = np.float32(1e-12)             # F.normalize's eps as the kernel holds it
+
+
+def ndcg_launch_shape(A, Q, max_segment):
+    """(n_pad, T, PER, alphas per block, alpha blocks) of a rerank_ndcg launch, by launch_rerank_ndcg's formulas
+    (blp_amd/csrc/rerank.hip)."""
+    n_pad = 64
+    while n_pad < max_segment:
+        n_pad <<= 1
+    T = min(max(n_pad >> 1, 64), 1024)
+    apb = min(max((A * Q + 2047) // 2048, 1), A)
+    return n_pad, T, n_pad // T, apb, -(-A // apb)
+
+
+def plain_ndcg_cut(s1, s2, gain, cand_ptr, alphas, cutoffs, idcg):
+    """blp_rerank_ndcg's contract as a loop per (alpha, query): (A, Q, n_cut) float64."""
+    out = np.zeros((len(alphas), len(cand_ptr) - 1, len(cutoffs)))
+    for a, alpha in enumerate(alphas):
+        alpha = float(alpha)
+        for q in range(len(cand_ptr) - 1):
+            lo, hi = int(cand_ptr[q]), int(cand_ptr[q + 1])
+            with np.errstate(over="ignore", invalid="ignore"):
+                f = [float(np.float32(alpha * float(s1[i]) + (1.0 - alpha) * float(s2[i]))) for i in range(lo, hi)]
+            # NaN last, then the C float descending (-0.0 == 0.0 as Python floats), then the lower index
+            order = sorted(range(hi - lo), key=lambda i: (1, 0.0, i) if math.isnan(f[i]) else (0, -f[i], i))
+            for j, k in enumerate(cutoffs):
+                dcg = 0.0
+                for r, i in enumerate(order[:k]):
+                    if gain[lo + i] > 0:
+                        dcg += int(gain[lo + i]) / math.log2(r + 2)
+                out[a, q, j] = dcg / idcg[q][j] if idcg[q][j] > 0 else 0.0
+    return out
+
+
+def plain_idcg(rels, cutoffs):
+    levels = sorted((int(r) for r in rels if r > 0), reverse=True)
+    out = []
+    for k in cutoffs:
+        acc = 0.0
+        for i, r in enumerate(levels[:k]):
+            acc += r / math.log2(i + 2)
+        out.append(acc)
+    return out
+
+
+def edge_segment():
+    """(s1 f32, s2 f64, gain) of one 12-candidate segment: NaN, -0 before +0, two f32 denormals (the smaller first), +inf
+    (NaN at alpha 0 and 1), -inf (NaN at alpha 1), 3e38 in both scores, an f32-only tie whose f64 order is the reverse of
+    the index order, -1e-45, and an f64 score that overflows f32.  The gains are distinct, so every change of order
+    changes the DCG at a cutoff past it."""
+    inf, nan = np.inf, np.nan
+    s1 = np.array([nan, -0.0, 0.0, 1e-42, 2e-42, inf, 0.0, 3e38, 1.0, 1.0, -1e-45, 0.0], np.float32)
+    s2 = np.array([1.0, -0.0, 0.0, 1e-42, 2e-42, inf, -inf, 3e38, 1.0, 1.0 + 1e-9, -1e-45, 1e39], np.float64)
+    gain = np.array([12, 2, 7, 3, 9, 4, 1, 6, 5, 11, 8, 10], np.int32)
+    return s1, s2, gain
+
+
+EDGE_ALPHAS = np.array([0.0, 0.25, 0.5, 1.0])
+EDGE_CUTOFFS = (1, 2, 3, 5, 8, 12, 100)
+
+
+def edge_floats(alpha):
+    """The C floats the edge segment is ranked by at ``alpha`` (numpy float32 scalars)."""
+    s1, s2, _ = edge_segment()
+    with np.errstate(over="ignore", invalid="ignore"):
+        return np.array([np.float32(alpha * float(a) + (1.0 - alpha) * float(b)) for a, b in zip(s1, s2)], np.float32)
+
+
+def embed_edge_segment(seed=11):
+    """The edge segment between ordinary ones (and an empty one): ptr, s1, s2, gain, the edge segment's query index."""
+    g = np.random.default_rng(seed)
+    lengths = [7, 0, 12, 70, 1]
+    ptr = np.concatenate(([0], np.cumsum(lengths))).astype(np.int64)
+    s1 = g.uniform(-1, 1, ptr[-1]).astype(np.float32)
+    s2 = g.uniform(5, 30, ptr[-1])
+    gain = g.integers(-1, 4, ptr[-1]).astype(np.int32)
+    s1[ptr[2]:ptr[3]], s2[ptr[2]:ptr[3]], gain[ptr[2]:ptr[3]] = edge_segment()
+    return ptr, s1, s2, gain, 2
+
+
+TIE_CUTOFFS = (3, 8192)
+
+
+def tie_segments():
+    """Segments whose keys all tie, so the index alone orders them: all NaN (100), all +inf at 0 < alpha < 1 (70), -0.0 and
+    +0.0 mixed (130), all equal at the full length (8192).  Gains: distinct ones on the first 3 indices (DCG@3 is theirs
+    alone only in index order) and on the last 10 (they take the last 10 ranks of DCG@8192 only in index order)."""
+    g = np.random.default_rng(5)
+    lengths = [100, 70, 130, 8192]
+    ptr = np.concatenate(([0], np.cumsum(lengths))).astype(np.int64)
+    s1, s2 = np.zeros(ptr[-1], np.float32), np.zeros(ptr[-1], np.float64)
+    s1[ptr[0]:ptr[1]], s2[ptr[0]:ptr[1]] = np.nan, 1.0
+    s1[ptr[1]:ptr[2]], s2[ptr[1]:ptr[2]] = np.inf, np.inf
+    signs = np.where(g.random(130) < 0.5, -0.0, 0.0)
+    s1[ptr[2]:ptr[3]], s2[ptr[2]:ptr[3]] = signs, signs
+    s1[ptr[3]:ptr[4]], s2[ptr[3]:ptr[4]] = 0.5, 0.5
+    gain = np.zeros(ptr[-1], np.int32)
+    for q in range(4):
+        gain[ptr[q]:ptr[q] + 3] = (3, 1, 2)
+        gain[ptr[q + 1] - 10:ptr[q + 1]] = g.permutation(10) + 1
+    return ptr, s1, s2, gain
+
+
+def plain_cosine_f64(table, queries, cand_ptr, cand_row):
+    """x . y / (max(|x|, 1e-12) max(|y|, 1e-12)) in float64, one candidate at a time (rows >= 0 only)."""
+    out = np.zeros(len(cand_row))
+    for q in range(len(cand_ptr) - 1):
+        y = queries[q].astype(np.float64)
+        for c in range(int(cand_ptr[q]), int(cand_ptr[q + 1])):
+            x = table[cand_row[c]].astype(np.float64)
+            out[c] = float(x @ y) / (max(math.sqrt(float(x @ x)), 1e-12) * max(math.sqrt(float(y @ y)), 1e-12))
+    return out
+
+
+SWEEP_SCALES = (1.0, 2.0 ** -20, 2.0 ** 30)
+SWEEP_LENGTHS = (3333, 1, 6000, 4000, 3000, 3666)
+
+
+def sqrt_sweep(scale):
+    """20 000 rows of six small integers times ``scale`` (a power of two) against one-hot queries: table, queries, ptr, rows,
+    the integer sums of squares, and the expected cosines from numpy float32 scalar operations alone.  The squares and
+    every partial sum of them are exact in f32 in any order, so the norm is the correctly rounded sqrt of a known float and
+    the cosine is fl(x_j / n) * 1.0 plus zeros.  The first rows are perfect squares (k, 0, ...) and Pythagorean pairs."""
+    g = np.random.default_rng(4)
+    ints = g.integers(-40, 41, (20000, 6))
+    squares = [[k, 0, 0, 0, 0, 0] for k in range(41)] + [[0, 3, 4, 0, 0, 0], [5, 0, -12, 0, 0, 0], [0, 0, 0, 8, 15, 0],
+                                                          [7, 24, 0, 0, 0, 0], [20, 0, 0, 0, 0, -21], [2, 4, 4, 0, 0, 0]]
+    ints[:len(squares)] = squares
+    s = np.float32(scale)
+    table = ints.astype(np.float32) * s
+    queries = np.eye(6, dtype=np.float32)
+    ptr = np.concatenate(([0], np.cumsum(SWEEP_LENGTHS))).astype(np.int64)
+    rows = np.arange(20000, dtype=np.int32)
+    sums = (ints * ints).sum(1)
+    norm = np.sqrt(sums.astype(np.float32) * s * s)   # exact product, then numpy's correctly rounded f32 square root
+    assert norm.dtype == np.float32
+    norm = np.where(norm < CLAMP, CLAMP, norm)
+    j = np.repeat(np.arange(6), SWEEP_LENGTHS)
+    want = (table[rows, j] / norm) * np.float32(1.0) + np.float32(0.0)
+    assert want.dtype == np.float32
+    return table, queries, ptr, rows, sums, want
+
+
+DEGENERATE_DIMS = (1, 13, 64, 70, 300)
+
+
+def degenerate_rows(D):
+    """{name: (D,) f32 row}: the rows at which a normalised dot product leaves ordinary arithmetic."""
+    g = np.random.default_rng(100 + D)
+    u, w = g.standard_normal(D), g.standard_normal(D)
+    u, w = u / np.linalg.norm(u), w / np.linalg.norm(w)
+    hot = np.zeros(D)
+    hot[0] = 1.0
+    below, above = np.nextafter(CLAMP, np.float32(0)), np.nextafter(CLAMP, np.float32(1))
+    rows = {
+        "u": u, "w": w, "hot": hot, "zero": np.zeros(D), "big": u * 1e18,
+        "nan": np.where(np.arange(D) == D // 2, np.nan, u), "inf": np.where(np.arange(D) == D // 2, np.inf, w),
+        "overflow": np.where(u < 0, -2e19, 2e19),  # every square overflows
+        "u1e20": u * 1e20,                          # the sum of squares overflows
+        "u1e-22": u * 1e-22,                        # denormal squares
+        "u1e-30": u * 1e-30,                        # squares underflow to 0: the norm is 0, clamped
+        "u1e-32": u * 1e-32, "w1e-32": w * 1e-32,   # clamped norms; the products of the normalised elements are denormal
+        "below": u * 0.999e-12, "above": w * 1.001e-12,  # general rows on either side of the clamp
+        "hot_below": hot * float(below), "hot_at": hot * float(CLAMP), "hot_above": hot * float(above),
+    }
+    with np.errstate(over="ignore"):
+        return {k: v.astype(np.float32) for k, v in rows.items()}
+
+
+def degenerate_cosine_problem(D):
+    """Every degenerate row as a table row and as a query row, every pair a candidate (plus one row -1 per query):
+    table, queries, ptr, rows, the row names."""
+    named = degenerate_rows(D)
+    names = list(named)
+    table = np.stack([named[k] for k in names])
+    n = len(names)
+    ptr = np.arange(n + 1, dtype=np.int64) * (n + 1)
+    rows = np.tile(np.concatenate((np.arange(n), [-1])), n).astype(np.int32)
+    return table, table.copy(), ptr, rows, names
+
+
+def test_plain_ndcg_reference_agrees_on_the_edge_segment():
+    s1, s2, gain = edge_segment()
+    f = edge_floats(0.5)
+    # the segment reaches what it is for: the C floats tie where the doubles do not, -0 and +0, denormals, the overflow
+    assert f[8] == f[9] and 0.5 * 1.0 + 0.5 * s2[8] < 0.5 * 1.0 + 0.5 * s2[9] and gain[8] != gain[9]
+    assert np.signbit(f[1]) and f[1] == 0 and not np.signbit(f[2]) and f[2] == 0 and gain[1] != gain[2]
+    assert 0 < f[3] < f[4] < F32_TINY and gain[3] != gain[4]
+    assert np.isnan(f[0]) and f[5] == np.inf and f[6] == -np.inf and f[11] == np.inf and s2[11] > np.finfo(np.float32).max
+    assert f[10] == -np.float32(1.4e-45) and np.isfinite(f[7]) and f[7] > 2.9e38
+    assert np.isnan(edge_floats(0.0)[5]) and np.isnan(edge_floats(1.0)[6]) and edge_floats(1.0)[11] == 0
+    ptr = np.array([0, 12])
+    idcg = [plain_idcg(list(gain) + [3], EDGE_CUTOFFS)]
+    want = plain_ndcg_cut(s1, s2, gain, ptr, EDGE_ALPHAS, EDGE_CUTOFFS, idcg)
+    got = R.trec_ndcg_cut(s1, s2, gain, ptr, EDGE_ALPHAS, EDGE_CUTOFFS, R.log2_table(100), np.array(idcg))
+    assert np.array_equal(got.view(np.int64), want.view(np.int64))
+    assert idcg[0] == R.ideal_dcg(list(gain) + [3], EDGE_CUTOFFS, R.log2_table(100))
+    # at alpha 0.5 the order is known by hand: +inf (5, 11 by index), 3e38, the f32 tie (8, 9 by index), the denormals
+    # (the larger first), -0 == +0 by index, -1e-45, -inf, NaN
+    order = [5, 11, 7, 8, 9, 4, 3, 1, 2, 10, 6, 0]
+    dcg = 0.0
+    for r, i in enumerate(order):
+        dcg += int(gain[i]) / math.log2(r + 2)
+    assert want[2, 0, 5] == dcg / idcg[0][5]
+
+
+def test_plain_ndcg_reference_agrees_embedded_and_on_tie_segments():
+    ptr, s1, s2, gain, _ = embed_edge_segment()
+    idcg = np.array([plain_idcg(gain[ptr[q]:ptr[q + 1]], EDGE_CUTOFFS) for q in range(len(ptr) - 1)])
+    want = plain_ndcg_cut(s1, s2, gain, ptr, EDGE_ALPHAS, EDGE_CUTOFFS, idcg)
+    got = R.trec_ndcg_cut(s1, s2, gain, ptr, EDGE_ALPHAS, EDGE_CUTOFFS, R.log2_table(100), idcg)
+    assert np.array_equal(got.view(np.int64), want.view(np.int64))
+    ptr, s1, s2, gain = tie_segments()
+    alphas = np.array([0.25, 0.5])
+    idcg = np.array([plain_idcg(gain[ptr[q]:ptr[q + 1]], TIE_CUTOFFS) for q in range(4)])
+    want = plain_ndcg_cut(s1, s2, gain, ptr, alphas, TIE_CUTOFFS, idcg)
+    got = R.trec_ndcg_cut(s1, s2, gain, ptr, alphas, TIE_CUTOFFS, R.log2_table(8192), idcg)
+    assert np.array_equal(got.view(np.int64), want.view(np.int64))
+    for q in range(4):  # index order: DCG@3 holds the first three gains alone, in their order
+        assert want[0, q, 0] == (3 / math.log2(2) + 1 / math.log2(3) + 2 / math.log2(4)) / idcg[q, 0]
+
+
+@pytest.mark.parametrize("D", [1, 13, 64, 65, 70, 128, 300, 768])
+def test_cosine_restated_close_to_plain_f64(D):
+    g = np.random.default_rng(D)
+    table = g.standard_normal((40, D)).astype(np.float32)
+    table *= np.array([1.0, 1e-10, 1e15, 3.0], np.float32)[np.arange(40) % 4, None]  # no square under- or overflows
+    queries = g.standard_normal((3, D)).astype(np.float32) * np.array([[1.0], [1e-8], [1e12]], np.float32)
+    ptr = np.array([0, 40, 40, 120])
+    rows = g.integers(0, 40, 120).astype(np.int32)
+    got = R.cosine_restated(table, queries, ptr, rows)
+    assert np.abs(got - plain_cosine_f64(table, queries, ptr, rows)).max() <= 1e-6
+
+
+@pytest.mark.parametrize("D", DEGENERATE_DIMS)
+def test_cosine_restated_rules_for_degenerate_rows(D):
+    table, queries, ptr, rows, names = degenerate_cosine_problem(D)
+    named = degenerate_rows(D)
+    n = len(names)
+    s = R.cosine_restated(table, queries, ptr, rows).reshape(n, n + 1)  # [query row, table row]
+    assert (s[:, n] == 0).all() and not np.signbit(s[:, n]).any()      # row -1
+    s = s[:, :n]
+    at = names.index
+    poisoned = [at("nan"), at("inf")]
+    assert np.isnan(s[poisoned]).all() and np.isnan(s[:, poisoned]).all()  # a NaN element, one inf element: NaN
+    clean = [i for i in range(n) if i not in poisoned]
+    assert np.isfinite(s[np.ix_(clean, clean)]).all()
+    for k in ("overflow", "u1e20"):  # the norm is inf, every element divides to 0: exactly +0.0 against a finite row
+        with np.errstate(over="ignore"):
+            assert np.isinf((named[k] * named[k]).sum())
+        for v in (s[at(k), clean], s[clean, at(k)]):
+            assert (v == 0).all() and not np.signbit(v).any()
+    # the clamp: a norm below 1e-12f divides by exactly 1e-12f, one at or above it by itself
+    v = {k: named[k][0] for k in ("hot_below", "hot_at", "hot_above")}
+    norm = {k: np.sqrt(v[k] * v[k]) for k in v}
+    assert norm["hot_below"] < CLAMP and norm["hot_at"] == CLAMP and norm["hot_above"] > CLAMP
+    assert all(type(x) is np.float32 for x in norm.values())
+    r = v["hot_below"] / CLAMP
+    assert r < 1 and s[at("hot"), at("hot_below")] == r == s[at("hot_below"), at("hot")]
+    assert s[at("hot_below"), at("hot_below")] == r * r
+    assert s[at("hot"), at("hot_at")] == 1.0 == s[at("hot"), at("hot_above")] == s[at("hot_above"), at("hot_at")]
+    assert np.linalg.norm(named["below"].astype(np.float64)) < 0.9995e-12
+    assert np.linalg.norm(named["above"].astype(np.float64)) > 1.0005e-12
+    assert abs(s[at("u"), at("below")] - 0.999) <= 1e-6  # 0.999e-12 u / 1e-12f against u
+    assert abs(s[at("w"), at("above")] - 1.0) <= 1e-6    # above the clamp: divided by its own norm
+    # denormal products: both norms clamp, (x_i / 1e-12f) * (y_i / 1e-12f) = 1e-40 u_i w_i
+    x, y = named["u1e-32"] / CLAMP, named["w1e-32"] / CLAMP
+    for k in ("u1e-32", "w1e-32", "u1e-30", "u1e-22"):
+        assert np.linalg.norm(named[k].astype(np.float64)) < 1e-13
+    prod = x * y
+    assert prod.dtype == np.float32 and ((prod != 0) & (np.abs(prod) < F32_TINY)).any()
+    got = s[at("u1e-32"), at("w1e-32")]  # [query, table row]: the sum of those products
+    assert got != 0 and abs(got) < F32_TINY
+
+
+@pytest.mark.parametrize("scale", SWEEP_SCALES)
+def test_cosine_restated_square_root_sweep(scale):
+    table, queries, ptr, rows, sums, want = sqrt_sweep(scale)
+    assert sums.max() >= 7000 and len(np.unique(sums)) >= 4000  # of at most 6 * 40 * 40 = 9600
+    roots = np.sqrt(sums.astype(np.float64))
+    assert (roots == np.round(roots)).sum() >= 47  # perfect squares among the sums
+    s = np.float32(scale)
+    norms = np.sqrt(R._tree_sum(table * table))
+    assert np.array_equal(norms, np.sqrt(sums.astype(np.float32) * s * s))
+    got = R.cosine_restated(table, queries, ptr, rows)
+    assert np.array_equal(got.view(np.int32), want.view(np.int32))
 
 
 # ------------------------------------------------------------------------------------------------ the C entry points
