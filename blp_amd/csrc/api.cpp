@@ -1172,8 +1172,9 @@ size_t blp_topk_sets_workspace_bytes(int model, int D, int64_t q_head, int64_t q
     return blp::topk_sets_workspace_bytes(model, D, q_head, q_tail, G, nnz, k);
 }
 
-// blp_topk_sets and blp_topk_sets_typed: the argument checks (messages under the entry's name `who`), then the launch
-static int topk_sets_call(const char* who, int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld,
+// blp_topk_sets, blp_topk_sets_typed and blp_topk_sets_wide: the argument checks (messages under the entry's name `who`), then
+// the launch (wide: topk_sets_wide.hip)
+static int topk_sets_call(const char* who, bool wide, int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld,
                           int64_t row_base, const float* source, int64_t S, int64_t ld_src, const int64_t* fixed_row,
                           const float* rel_emb, int64_t R, const int64_t* rel_id, int64_t q_head, int64_t q_tail, int k,
                           const int64_t* set_ptr, const int64_t* set_row, int64_t nnz, int64_t G, const int64_t* qset_ptr_head,
@@ -1182,7 +1183,10 @@ static int topk_sets_call(const char* who, int model, const void* table, int tab
     if (!valid_model(model)) return fail(BLP_ERR_BAD_ARG, "%s: unknown model %d", who, model);
     if (!valid_table_dtype(table_dtype)) return fail(BLP_ERR_BAD_ARG, "%s: unknown table dtype %d", who, table_dtype);
     if (k < 1 || k > 256) return fail(BLP_ERR_BAD_ARG, "%s: k = %d outside [1, 256]", who, k);
-    if (!blp_topk_sets_supported(model, D, k))
+    if (wide && !blp_topk_sets_wide_supported(model, table_dtype, D, k))
+        return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: model %d at D = %d not supported (transe, D %% 4 == 0, 4 <= D <= 1024: see blp_topk_sets_wide_supported)",
+                    who, model, D);
+    if (!wide && !blp_topk_sets_supported(model, D, k))
         return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (64 / 128 / 256: see blp_topk_sets_supported)", who, D);
     if (N < 0 || q_head < 0 || q_tail < 0 || ld < D || row_base < 0 || nnz < 0 || G < 0)
         return fail(BLP_ERR_BAD_ARG, "%s: negative size / row_base or ld < D (N=%lld q_head=%lld q_tail=%lld ld=%lld nnz=%lld G=%lld)", who,
@@ -1216,7 +1220,8 @@ static int topk_sets_call(const char* who, int model, const void* table, int tab
         spec.row_base = filter->row_base;
     }
     if (Q == 0) return BLP_OK;
-    const size_t need = blp::topk_sets_workspace_bytes(model, D, q_head, q_tail, G, nnz, k);
+    const size_t need = wide ? blp::topk_sets_wide_workspace_bytes(D, q_head, q_tail, G, nnz, k)
+                             : blp::topk_sets_workspace_bytes(model, D, q_head, q_tail, G, nnz, k);
     if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255u))
         return fail(BLP_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned and >= %zu bytes (got %zu)", who, need, workspace_bytes);
     DeviceGuard guard(device);
@@ -1224,10 +1229,11 @@ static int topk_sets_call(const char* who, int model, const void* table, int tab
     int cu = 0;
     if (int rc = compute_units(device, &cu)) return rc;
     const blp::SetLookup sets{set_ptr, set_row, qset_ptr_head, qset_ptr_tail, G, row_base};
-    hipError_t err = blp::launch_topk_sets(model, D, table_dtype, table, N, ld, blp::QRows::rows_of(source, fixed_row, ld_src),
+    hipError_t err = (wide ? blp::launch_topk_sets_wide : blp::launch_topk_sets)(model, D, table_dtype, table, N, ld, blp::QRows::rows_of(source, fixed_row, ld_src),
                                            blp::QRows::rows_of(rel_emb, rel_id, D), q_head, q_tail, k, sets, nnz, spec, rows, scores,
                                            workspace, cu, static_cast<hipStream_t>(stream));
-    if (err != hipSuccess) return hip_fail(err, table_dtype == BLP_DTYPE_F32 ? "blp_topk_sets launch" : "blp_topk_sets_typed launch");
+    if (err != hipSuccess)
+        return hip_fail(err, wide ? "blp_topk_sets_wide launch" : table_dtype == BLP_DTYPE_F32 ? "blp_topk_sets launch" : "blp_topk_sets_typed launch");
     return BLP_OK;
 }
 
@@ -1236,7 +1242,7 @@ int blp_topk_sets(int model, const float* table, int64_t N, int D, int64_t ld, i
                   int64_t q_tail, int k, const int64_t* set_ptr, const int64_t* set_row, int64_t nnz, int64_t G,
                   const int64_t* qset_ptr_head, const int64_t* qset_ptr_tail, const blp_filter* filter, int64_t* rows, float* scores,
                   void* workspace, size_t workspace_bytes, int device, void* stream) {
-    return topk_sets_call("blp_topk_sets", model, table, BLP_DTYPE_F32, N, D, ld, row_base, source, S, ld_src, fixed_row, rel_emb, R,
+    return topk_sets_call("blp_topk_sets", false, model, table, BLP_DTYPE_F32, N, D, ld, row_base, source, S, ld_src, fixed_row, rel_emb, R,
                           rel_id, q_head, q_tail, k, set_ptr, set_row, nnz, G, qset_ptr_head, qset_ptr_tail, filter, rows, scores,
                           workspace, workspace_bytes, device, stream);
 }
@@ -1256,9 +1262,32 @@ int blp_topk_sets_typed(int model, const void* table, int table_dtype, int64_t N
                         const int64_t* rel_id, int64_t q_head, int64_t q_tail, int k, const int64_t* set_ptr, const int64_t* set_row,
                         int64_t nnz, int64_t G, const int64_t* qset_ptr_head, const int64_t* qset_ptr_tail, const blp_filter* filter,
                         int64_t* rows, float* scores, void* workspace, size_t workspace_bytes, int device, void* stream) {
-    return topk_sets_call(table_dtype == BLP_DTYPE_F32 ? "blp_topk_sets" : "blp_topk_sets_typed", model, table, table_dtype, N, D, ld,
+    return topk_sets_call(table_dtype == BLP_DTYPE_F32 ? "blp_topk_sets" : "blp_topk_sets_typed", false, model, table, table_dtype, N, D, ld,
                           row_base, source, S, ld_src, fixed_row, rel_emb, R, rel_id, q_head, q_tail, k, set_ptr, set_row, nnz, G,
                           qset_ptr_head, qset_ptr_tail, filter, rows, scores, workspace, workspace_bytes, device, stream);
+}
+
+// ---- filtered top-k inside candidate sets shared between queries, TransE at any width (topk_sets_wide.hip)
+int blp_topk_sets_wide_supported(int model, int table_dtype, int D, int k) {
+    return valid_model(model) && blp::topk_sets_wide_supported(model, table_dtype, D, k) ? 1 : 0;
+}
+
+size_t blp_topk_sets_wide_workspace_bytes(int model, int table_dtype, int D, int64_t q_head, int64_t q_tail, int64_t G, int64_t nnz,
+                                          int k) {
+    if (!blp_topk_sets_wide_supported(model, table_dtype, D, k) || q_head < 0 || q_tail < 0 || G < 0 || nnz < 0 || nnz >= (1ll << 31) ||
+        q_head + q_tail > (1ll << 31) / k)
+        return 0;
+    return blp::topk_sets_wide_workspace_bytes(D, q_head, q_tail, G, nnz, k);
+}
+
+int blp_topk_sets_wide(int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld, int64_t row_base,
+                       const float* source, int64_t S, int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R,
+                       const int64_t* rel_id, int64_t q_head, int64_t q_tail, int k, const int64_t* set_ptr, const int64_t* set_row,
+                       int64_t nnz, int64_t G, const int64_t* qset_ptr_head, const int64_t* qset_ptr_tail, const blp_filter* filter,
+                       int64_t* rows, float* scores, void* workspace, size_t workspace_bytes, int device, void* stream) {
+    return topk_sets_call("blp_topk_sets_wide", true, model, table, table_dtype, N, D, ld, row_base, source, S, ld_src, fixed_row, rel_emb,
+                          R, rel_id, q_head, q_tail, k, set_ptr, set_row, nnz, G, qset_ptr_head, qset_ptr_tail, filter, rows, scores,
+                          workspace, workspace_bytes, device, stream);
 }
 
 // ---- re-ranking a retrieval run (rerank.hip)

@@ -151,6 +151,15 @@ hipError_t launch_topk_sets(int model, int D, int dtype, const void* table, int6
                             const QRows q_rel, int64_t q_head, int64_t q_tail, int k, const SetLookup& sets, int64_t nnz,
                             const FilterSpec& filter, int64_t* rows, float* scores, void* workspace, int n_cu, hipStream_t stream);
 
+// topk_sets_wide.hip: the same call for TransE at any width (D % 4 == 0, 4 <= D <= 1024; include/blp_hip.h:
+// blp_topk_sets_wide): same arguments; the workspace -- the same for every dtype -- holds the coefficient rows (head side
+// 2 D floats per query, tail side D), the G + 1 values of the unit prefix and the (Q, S_max, k) partial lists
+bool topk_sets_wide_supported(int model, int dtype, int D, int k);
+size_t topk_sets_wide_workspace_bytes(int D, int64_t q_head, int64_t q_tail, int64_t G, int64_t nnz, int k);
+hipError_t launch_topk_sets_wide(int model, int D, int dtype, const void* table, int64_t N, int64_t ld, const QRows q_fixed,
+                                 const QRows q_rel, int64_t q_head, int64_t q_tail, int k, const SetLookup& sets, int64_t nnz,
+                                 const FilterSpec& filter, int64_t* rows, float* scores, void* workspace, int n_cu, hipStream_t stream);
+
 // ---- the bounded worst case of the pre-pass paths (round 5) --------------------------------------------------------------
 // A pre-pass pays off while it leaves little to the exact path.  When a device-side counter says it has not -- the pair lists
 // ran (nearly) full: exact ties with the true entity on whole percents of the table -- the refinement kernels stand down and

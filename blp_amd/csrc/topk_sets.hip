@@ -52,16 +52,8 @@ namespace blp {
 
 constexpr int kTopkSetsScanThreads = 1024;
 
-// S_max, the partial lists per query: n_slabs x (a lower bound of the chunks) <= max(chunks, kTopkTargetGroups), and at
-// most one per kTopkWaves tiles of all the sets' entries together -- topk_slabs' rule (topk.hip) with nnz in N's place.
-static int64_t topk_sets_slabs(int64_t Q, int64_t nnz, int k) {
-    const int64_t chunks = (Q + topk_chunk(k) - 1) / topk_chunk(k);
-    const int64_t tiles = (nnz + kTileRows - 1) / kTileRows;
-    int64_t s = chunks > 0 ? kTopkTargetGroups / chunks : 1;
-    const int64_t cap = (tiles + kTopkWaves - 1) / kTopkWaves;
-    if (s > cap) s = cap;
-    return s < 1 ? 1 : s;
-}
+// S_max, the partial lists per query: topk_sets_slabs_rule (topk_sets_kernel.h) for chunks of topk_chunk(k) queries
+static int64_t topk_sets_slabs(int64_t Q, int64_t nnz, int k) { return topk_sets_slabs_rule(Q, nnz, topk_chunk(k)); }
 
 __global__ __launch_bounds__(kTopkSetsScanThreads) void topk_sets_unit_prefix_kernel(const int64_t* __restrict__ set_ptr,
                                                                                      const int64_t* __restrict__ qptr_head,
@@ -101,6 +93,12 @@ __global__ __launch_bounds__(kTopkSetsScanThreads) void topk_sets_unit_prefix_ke
 }
 
 // ------------------------------------------------------------------------------------------------ host side
+hipError_t launch_topk_sets_unit_prefix(const SetLookup& sets, int q_chunk, int s_max, int64_t* prefix, hipStream_t stream) {
+    topk_sets_unit_prefix_kernel<<<1, kTopkSetsScanThreads, 0, stream>>>(sets.set_ptr, sets.qptr_head, sets.qptr_tail, sets.G, q_chunk,
+                                                                         s_max, prefix);
+    return hipGetLastError();
+}
+
 bool topk_sets_supported(int model, int D, int k) { return topk_supported(model, D, k); }
 bool topk_sets_typed_supported(int model, int dtype, int D, int k) {
     return (dtype == kTableF32 || dtype == kTableF16 || dtype == kTableBF16) && topk_sets_supported(model, D, k);
@@ -147,9 +145,7 @@ hipError_t launch_topk_sets(int model, int D, int dtype, const void* table, int6
     hipError_t err = launch_prep_coef(model, D, q_fixed, q_rel, q_head, q_tail, w.coef_head, w.coef_tail, stream);
     if (err != hipSuccess) return err;
     if ((err = hipMemsetAsync(w.partial, 0, w.partial_bytes, stream)) != hipSuccess) return err;
-    topk_sets_unit_prefix_kernel<<<1, kTopkSetsScanThreads, 0, stream>>>(sets.set_ptr, sets.qptr_head, sets.qptr_tail, sets.G, q_chunk,
-                                                                         s_max, w.prefix);
-    if ((err = hipGetLastError()) != hipSuccess) return err;
+    if ((err = launch_topk_sets_unit_prefix(sets, q_chunk, s_max, w.prefix, stream)) != hipSuccess) return err;
     err = hipErrorInvalidValue;
     if (dtype != kTableF32) {
         err = launch_topk_sets_pass16(model, D, dtype, table, N, ld, w, q_head, sets, q_chunk, s_max, k, filter, n_cu, stream);

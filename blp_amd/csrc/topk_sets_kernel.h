@@ -180,6 +180,21 @@ static hipError_t topk_sets_pass(const TE* table, int64_t N, int64_t ld, const T
     return hipGetLastError();
 }
 
+// S_max, the partial lists per query, for chunks of q_chunk queries: n_slabs x (a lower bound of the chunks) <=
+// max(chunks, kTopkTargetGroups), and at most one per kTopkWaves tiles of all the sets' entries together -- topk_slabs' rule
+// (topk.hip) with nnz in N's place.  From Q, nnz and q_chunk alone: computed on the host.
+inline int64_t topk_sets_slabs_rule(int64_t Q, int64_t nnz, int q_chunk) {
+    const int64_t chunks = (Q + q_chunk - 1) / q_chunk;
+    const int64_t tiles = (nnz + kTileRows - 1) / kTileRows;
+    int64_t s = chunks > 0 ? kTopkTargetGroups / chunks : 1;
+    const int64_t cap = (tiles + kTopkWaves - 1) / kTopkWaves;
+    if (s > cap) s = cap;
+    return s < 1 ? 1 : s;
+}
+
+// topk_sets.hip: topk_sets_unit_prefix_kernel's launch (one workgroup; G + 1 values into prefix), for topk_sets_wide.hip too
+hipError_t launch_topk_sets_unit_prefix(const SetLookup& sets, int q_chunk, int s_max, int64_t* prefix, hipStream_t stream);
+
 // topk_sets16.hip: the selection pass over a 16-bit table (dtype: kTableF16 / kTableBF16; ld in elements)
 hipError_t launch_topk_sets_pass16(int model, int D, int dtype, const void* table, int64_t N, int64_t ld, const TopkSetsWorkspace& w,
                                    int64_t q_head, const SetLookup& sets, int q_chunk, int s_max, int k, const FilterSpec& filter,

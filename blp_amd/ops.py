@@ -8,6 +8,7 @@ device memory and the stream; every arithmetic step of the hot path runs in the 
     rank_sets(...)      counts against candidate sets shared by groups of queries (type-constrained evaluation)
     rank_sets_wide(...) the same for TransE at any width D % 4 == 0, 4 <= D <= 1024 (the BOW / DKRL 300 and 768)
     topk_sets(...)      filtered top-k prediction inside candidate sets shared by groups of queries
+    topk_sets_wide(...) the same for TransE at any width D % 4 == 0, 4 <= D <= 1024 (the BOW / DKRL 300 and 768)
     rerank_cosine(...)  cosine of every retrieval candidate with its query (retrieval.py:170-175)
     rerank_ndcg(...)    trec_eval ndcg_cut of every (alpha, query) of a re-ranked run (retrieval.py:139-258)
     score(...)          score_fn(heads, tails, rels)       (models.py:222-248), differentiable
@@ -631,11 +632,46 @@ def topk_sets(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, 
     the query's set: the k entries with the highest score_fn value (descending score, ties by ascending row, NaN last), the
     rows ``filter`` (a SegmentFilter whose row_base is ``row_base``) names removed; slots beyond the entries left: row -1,
     score NaN.  Returns (rows (Q, k) int64, scores (Q, k) float32) in the caller's (grouped) order; ``out`` may give both."""
+    return _topk_sets(False, rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, set_ptr, set_rows, qset_ptr_head,
+                      qset_ptr_tail, filter, row_base, out)
+
+
+def topk_sets_wide_supported(rel_model, dim, k, dtype=torch.float32):
+    """True if topk_sets_wide takes this width, k and table dtype (blp_topk_sets_wide_supported: transe, D % 4 == 0,
+    4 <= D <= 1024 -- the BOW / DKRL encoders' 300 and 768 --, 1 <= k <= 256; a float32, float16 or bfloat16 table)."""
+    if dtype not in TABLE_DTYPES:
+        return False
+    return bool(_lib.lib().blp_topk_sets_wide_supported(_lib.MODEL_IDS[rel_model], TABLE_DTYPES[dtype], int(dim), int(k)))
+
+
+def topk_sets_wide_workspace_bytes(rel_model, D, q_head, q_tail, num_sets, nnz, k, dtype=torch.float32):
+    """Bytes of topk_sets_wide's workspace: coefficient rows, num_sets + 1 unit offsets and the partial lists -- never a function
+    of the table's length or its storage type (0: not supported, or a negative size)."""
+    if dtype not in TABLE_DTYPES:
+        return 0
+    return int(_lib.lib().blp_topk_sets_wide_workspace_bytes(_lib.MODEL_IDS[rel_model], TABLE_DTYPES[dtype], int(D), int(q_head),
+                                                            int(q_tail), int(num_sets), int(nnz), int(k)))
+
+
+def topk_sets_wide(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, set_ptr, set_rows, qset_ptr_head, qset_ptr_tail,
+                   filter=None, row_base=0, out=None):
+    """topk_sets for TransE at any width D % 4 == 0, 4 <= D <= 1024 (blp_topk_sets_wide: a lane holds 64 columns of its set row at
+    a time and the running sums of a chunk of up to 16 queries of the set's group; the winners' scores come straight from the
+    selection keys): same arguments, same rows and scores -- the reference's bit for bit, on a 16-bit table those of the table
+    widened to float32."""
+    return _topk_sets(True, rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, set_ptr, set_rows, qset_ptr_head,
+                      qset_ptr_tail, filter, row_base, out)
+
+
+def _topk_sets(wide, rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, set_ptr, set_rows, qset_ptr_head, qset_ptr_tail,
+               filter, row_base, out):
+    """topk_sets (blp_topk_sets_typed) and topk_sets_wide (blp_topk_sets_wide): one argument handling, two entries."""
+    who = "topk_sets_wide" if wide else "topk_sets"
     _require_device(table, source, fixed_row, rel_emb, rel_ids, set_ptr, set_rows, qset_ptr_head, qset_ptr_tail)
     if table.dtype not in TABLE_DTYPES:
-        raise TypeError(f"topk_sets reads a float32, float16 or bfloat16 table, got {table.dtype}")
+        raise TypeError(f"{who} reads a float32, float16 or bfloat16 table, got {table.dtype}")
     if source.dtype != torch.float32:
-        raise TypeError(f"topk_sets needs a float32 `source` for the queries' vectors, got {source.dtype}")
+        raise TypeError(f"{who} needs a float32 `source` for the queries' vectors, got {source.dtype}")
     same = source is table
     table = _table_rows(table, "table")
     source = table if same else _f32_rows(source, "source")
@@ -654,10 +690,13 @@ def topk_sets(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, 
         raise ValueError("set_ptr, qset_ptr_head and qset_ptr_tail need G + 1 entries each")
     if not 0 <= q_head <= Q:
         raise ValueError(f"q_head = {q_head} outside [0, {Q}]")
-    if not topk_sets_supported(rel_model, D, k, table.dtype):
+    if wide and not topk_sets_wide_supported(rel_model, D, k, table.dtype):
+        raise ValueError(f"topk_sets_wide: {rel_model} at D = {D}, k = {k} not supported (transe, D % 4 == 0, 4 <= D <= 1024, "
+                         "1 <= k <= 256): see topk_sets_wide_supported")
+    if not wide and not topk_sets_supported(rel_model, D, k, table.dtype):
         raise ValueError(f"topk_sets: D = {D}, k = {k} not supported (D in 64 / 128 / 256, 1 <= k <= 256): see topk_sets_supported")
     if filter is not None and int(filter.row_base) != int(row_base):
-        raise ValueError(f"topk_sets: the filter's row_base {filter.row_base} differs from row_base {row_base}")
+        raise ValueError(f"{who}: the filter's row_base {filter.row_base} differs from row_base {row_base}")
     dev = table.device
     if out is None:
         out = (torch.empty((Q, k), dtype=torch.int64, device=dev), torch.empty((Q, k), dtype=torch.float32, device=dev))
@@ -671,17 +710,17 @@ def topk_sets(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, 
     model = _lib.MODEL_IDS[rel_model]
     stream = torch._C._cuda_getCurrentRawStream(dev.index)
     tdt = TABLE_DTYPES[table.dtype]
-    ws_bytes = L.blp_topk_sets_typed_workspace_bytes(model, tdt, D, q_head, Q - q_head, G, nnz, k)
+    ws_bytes = (L.blp_topk_sets_wide_workspace_bytes if wide else L.blp_topk_sets_typed_workspace_bytes)(model, tdt, D, q_head, Q - q_head, G, nnz, k)
     workspace = _workspace(dev, stream, ws_bytes)
     spec = None if filter is None else _filter_spec(filter, Q, dev)
-    status = L.blp_topk_sets_typed(model, table.data_ptr(), tdt, N, D, table.stride(0) if tdt or N > 1 else D, int(row_base),
+    status = (L.blp_topk_sets_wide if wide else L.blp_topk_sets_typed)(model, table.data_ptr(), tdt, N, D, table.stride(0) if tdt or N > 1 else D, int(row_base),
                                    source.data_ptr(), source.shape[0], source.stride(0) if source.shape[0] > 1 else D,
                                    fixed_row.data_ptr(), rel_emb.data_ptr(), rel_emb.shape[0], rel_ids.data_ptr(), q_head, Q - q_head, k,
                                    set_ptr.data_ptr(), _addr(set_rows) if nnz else None, nnz, G, qset_ptr_head.data_ptr(),
                                    qset_ptr_tail.data_ptr(), spec, rows.data_ptr(), scores.data_ptr(), workspace.data_ptr(), ws_bytes,
                                    dev.index, stream)
     if status:
-        _lib.check(status, "blp_topk_sets_typed" if tdt else "blp_topk_sets")
+        _lib.check(status, "blp_topk_sets_wide" if wide else "blp_topk_sets_typed" if tdt else "blp_topk_sets")
     return rows, scores
 
 

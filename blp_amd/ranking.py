@@ -1285,8 +1285,9 @@ def _topk_sets_dense(score_fn, table, fixed, rel, q_head, k, set_ptr, set_rows, 
                      max_bytes=1 << 28):
     """The dense route of predict_links_in_sets: score_fn of each set's gathered rows against its group's queries, in (query
     chunk, row slab) pieces of bounded bytes, the filter through _filtered_pairs, the order by _stable_topk.  Queries grouped by
-    set within each side, as blp_topk_sets takes them; fixed / rel (Q, D) float32.  CPU tensors and the widths and k
-    blp_topk_sets / blp_topk_sets_typed do not take; on CPU tensors it is the oracle of the fused route.  Returns (rows (Q, k) int64 global rows,
+    set within each side, as blp_topk_sets takes them; fixed / rel (Q, D) float32.  CPU tensors and the widths and k that
+    neither blp_topk_sets / blp_topk_sets_typed nor blp_topk_sets_wide take (the bilinear models off 64 / 128 / 256, k > 256); on
+    CPU tensors it is the oracle of the fused routes.  Returns (rows (Q, k) int64 global rows,
     scores (Q, k) float32)."""
     Q, (N, D) = fixed.shape[0], table.shape
     dev = table.device
@@ -1341,8 +1342,10 @@ def predict_links_in_sets(model, table, triples, k, sets, ent2idx, *, set_ids=No
     ties by ascending row, NaN last; -1 / NaN beyond the entries of the set that are left.  Scores are score_fn's values bit
     for bit (of the table widened to float32).  A float32, float16 or bfloat16 HIP table at 64 / 128 / 256 and k <= 256 goes
     through blp_topk_sets / blp_topk_sets_typed (a row of a set is fetched once per chunk of its group's queries; a 16-bit
-    table is read as it is, only the Q fixed rows are gathered and widened); CPU tensors, other widths and k > 256 take the
-    dense route: score_fn on gathered rows and a stable sort."""
+    table is read as it is, only the Q fixed rows are gathered and widened).  A HIP table at any other width blp_topk_sets_wide
+    takes -- TransE, D % 4 == 0, 4 <= D <= 1024: the BOW / DKRL 300 and 768 -- and k <= 256 goes through blp_topk_sets_wide (a row
+    of a set fetched once per chunk of up to 16 queries of its group).  CPU tensors, the bilinear models at other widths and
+    k > 256 take the dense route: score_fn on gathered rows and a stable sort."""
     model = _module(model)
     if side not in ("head", "tail", "both"):
         raise ValueError(f"side must be 'head', 'tail' or 'both', got {side!r}")
@@ -1387,7 +1390,12 @@ def predict_links_in_sets(model, table, triples, k, sets, ent2idx, *, set_ids=No
         sel = torch.cat([x for x, on in ((torch.arange(T, device=device), heads), (torch.arange(T, 2 * T, device=device), tails)) if on])[perm]
         filt = ops.SegmentFilter(seg.seg_lo[sel].contiguous(), seg.seg_hi[sel].contiguous(), seg.values,
                                  seg.exclude[sel].contiguous(), seg.ent2idx, 0)
+    fused = None
     if table.is_cuda and k <= 256 and ops.topk_sets_supported(model.rel_model, D, k, table.dtype):
+        fused = ops.topk_sets
+    elif table.is_cuda and k <= 256 and ops.topk_sets_wide_supported(model.rel_model, D, k, table.dtype):
+        fused = ops.topk_sets_wide
+    if fused is not None:
         if table.dtype != torch.float32:
             # float32 query vectors: the Q fixed rows gathered and widened (exact) by the library's own kernel
             # (blp_gather_triple_vectors: 64-bit offsets, a table of more than 2^31 bytes included)
@@ -1395,8 +1403,8 @@ def predict_links_in_sets(model, table, triples, k, sets, ent2idx, *, set_ids=No
             source, src_fixed = ops.gather_triple_vectors(pairs, None, table)[:Q], torch.arange(Q, device=device)
         else:
             source, src_fixed = table, g_fixed
-        g_rows, g_scores = ops.topk_sets(model.rel_model, table, source, src_fixed, rel_w, g_rel, q_head, k, set_ptr, set_rows,
-                                         qptr_head, qptr_tail, filter=filt)
+        g_rows, g_scores = fused(model.rel_model, table, source, src_fixed, rel_w, g_rel, q_head, k, set_ptr, set_rows, qptr_head,
+                                 qptr_tail, filter=filt)
     else:
         dense_filt = None if filt is None else (filt.seg_lo, filt.seg_hi, filt.values, filt.exclude, filt.ent2idx)
         g_rows, g_scores = _topk_sets_dense(model.score_fn, table, table[g_fixed].float(), rel_w[g_rel], q_head, k, set_ptr,

@@ -684,6 +684,38 @@ int blp_topk_sets_typed(int model, const void *table, int table_dtype, int64_t N
                         const int64_t *set_row, int64_t nnz, int64_t G, const int64_t *qset_ptr_head,
                         const int64_t *qset_ptr_tail, const blp_filter *filter, int64_t *rows, float *scores, void *workspace,
                         size_t workspace_bytes, int device, void *stream);
+/* Filtered top-k inside candidate sets shared between queries for TransE at ANY width: blp_topk_sets_wide is
+ * blp_topk_sets_typed -- the contract above word for word: the sets CSR of strictly ascending global rows, row_base shards with
+ * entries outside [row_base, row_base + N) skipped (shards merged by blp_topk_merge equal the unsharded call), the grouping by
+ * qset_ptr_head / qset_ptr_tail, the filter (rows removed, exclude[q] never), the (Q, k) rows and scores in grouped order:
+ * descending score, ties by ascending row, NaN last, left-over slots -1 / quiet NaN; scores are the reference's f32 score_fn
+ * bit for bit, sign of zero included (a 16-bit table: of the table widened to f32) -- at the widths blp_topk_sets_supported
+ * refuses: the BOW / DKRL encoders' 300 and 768.  A lane holds 64 columns of its set row at a time and the running sums of a
+ * chunk of min(16, what the lists' LDS holds at this k) queries of the set's group (topk_sets_wide.hip): 16 for k <= 48, 12 at
+ * k = 64, 4 at k = 192, 3 at k = 256.  The winners' scores come straight from the selection keys: there is no re-scoring pass.
+ * Limits (blp_topk_sets_wide_supported): BLP_MODEL_TRANSE only, table_dtype a BLP_DTYPE_*, D % 4 == 0 and 4 <= D <= 1024 --
+ * 64 / 128 / 256 included, where it is a second implementation of the same bits (blp_topk_sets is the faster one: chunks of up
+ * to 32 queries); 1 <= k <= 256; the other models, other widths and unknown dtypes answer 0.  Q x k < 2^31; nnz < 2^31;
+ * row_base + N <= 2^31; table / source / rel_emb 16-byte aligned, ld % 4 == 0 (f32) or ld % 8 == 0 (a 16-bit table, in
+ * elements), ld_src % 4 == 0.  Status codes, messages and the order of the checks as blp_topk_sets_typed; every check runs
+ * before a device is touched.
+ * Workspace: blp_topk_sets_wide_workspace_bytes(model, table_dtype, D, q_head, q_tail, G, nnz, k) bytes (0 where unsupported
+ * or a size is negative), 256-B aligned: per-query coefficient rows (2 D floats per head-replacing query, D per tail-replacing
+ * one), G + 1 int64 of work-unit offsets and the partial lists of k 8-byte keys -- at most Q + 8 192 of them whatever nnz --,
+ * each part rounded up to 256 bytes.  It does not depend on N or on the table's type, never shrinks when Q, G, k or nnz grow,
+ * and is <= 8 (D + k) Q + 8 (G + 1) + 4 MiB bytes.
+ * Asynchronous on `stream`, no host synchronisation, no allocation; nothing about set or group sizes is read on the host.
+ * Deterministic: a query's result is the set of its k largest keys, so nothing depends on the grid.
+ * (Added after 6.0.0 without a version change: no existing entry point changed.) */
+int blp_topk_sets_wide_supported(int model, int table_dtype, int D, int k);
+size_t blp_topk_sets_wide_workspace_bytes(int model, int table_dtype, int D, int64_t q_head, int64_t q_tail, int64_t G,
+                                          int64_t nnz, int k);
+int blp_topk_sets_wide(int model, const void *table, int table_dtype, int64_t N, int D, int64_t ld, int64_t row_base,
+                       const float *source, int64_t S, int64_t ld_src, const int64_t *fixed_row, const float *rel_emb, int64_t R,
+                       const int64_t *rel_id, int64_t q_head, int64_t q_tail, int k, const int64_t *set_ptr,
+                       const int64_t *set_row, int64_t nnz, int64_t G, const int64_t *qset_ptr_head,
+                       const int64_t *qset_ptr_tail, const blp_filter *filter, int64_t *rows, float *scores, void *workspace,
+                       size_t workspace_bytes, int device, void *stream);
 
 /* --------------------------------------------------------------------------------------------
  * Filtered top-k INSIDE per-query candidate lists: ANSWER a query (h, r, ?) / (?, r, t) with the k entries of ITS OWN LIST
