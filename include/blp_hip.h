@@ -142,7 +142,8 @@ int blp_rank_all_supported(int model, int D, int64_t q_head, int64_t q_tail);
  * (2B, N) mask copied to the device) needs no per-batch list at all:
  *   the graph's edges are sorted once by key (head, rel) with value tail -- and by (tail, rel) with value
  *   head -- into one `values` array of ENTITY IDS (blp_amd.utils.FilterIndex); for query q the caller
- *   binary-searches the key of its triple and passes the slice [seg_lo[q], seg_hi[q]) of `values`;
+ *   binary-searches the key of its triple and passes the slice [seg_lo[q], seg_hi[q]) of `values` (empty when
+ *   seg_hi[q] <= seg_lo[q]; `values` is then never read);
  *   exclude[q] is the triple's own entity at the replaced position, which is never filtered (utils.py:71,78);
  *   ent2idx (utils.make_ent2idx, utils.py:31-43) maps an entity id to its table row, -1 (or an id beyond
  *   ent2idx_len) = not a candidate (utils.py:72,79); NULL = the values are table rows already;
@@ -254,7 +255,8 @@ int blp_rank_all_prepass_stats(int model, int64_t N, int D, int64_t q_head, int6
  * true entity given per query as a column index (true_idx, the reference's `true_ents`,
  * utils.py:102) or as a score (true_score); exactly one of the two.  Replaces utils.py:103-105 and the
  * filtered overwrite train.py:159-167 for callers that materialise pred_ents, and serves embedding
- * widths the fused kernels are not compiled for (the matrix then comes from blp_score_fwd). */
+ * widths the fused kernels are not compiled for (the matrix then comes from blp_score_fwd).  filt_rowptr (Q + 1) / filt_col:
+ * the CSR of the columns the filtered setting removes (both NULL: none); a column outside [0, N) is ignored. */
 int blp_rank_from_scores(const float *scores, int64_t Q, int64_t N, int64_t ld, const int64_t *true_idx,
                          const float *true_score, const int64_t *filt_rowptr, const int64_t *filt_col,
                          int32_t *counts, int device, void *stream);
