@@ -137,7 +137,8 @@ int blp_build_queries(const blp_queries* q, int device, void* stream) {
     if (!aligned16(q->source) || !aligned16(q->rel_emb) || !aligned16(q->q_fixed) || !aligned16(q->q_rel) || (q->ld & 3) || q->ld < q->D)
         return fail(BLP_ERR_BAD_ARG, "blp_build_queries: source / rel_emb / q_fixed / q_rel must be 16-byte aligned, ld %% 4 == 0, ld >= D");
     const bool with_index = q->heads_key || q->tails_key || q->seg_lo || q->seg_hi || q->exclude;
-    if (with_index && (!q->seg_lo || !q->seg_hi || !q->exclude || q->index_R <= 0 || q->n_heads < 0 || q->n_tails < 0 ||
+    // (n == 0: the outputs are empty arrays, which a caller may well hand over as NULL)
+    if (with_index && ((q->n > 0 && (!q->seg_lo || !q->seg_hi || !q->exclude)) || q->index_R <= 0 || q->n_heads < 0 || q->n_tails < 0 ||
                        (q->n_heads > 0 && !q->heads_key) || (q->n_tails > 0 && !q->tails_key)))
         return fail(BLP_ERR_BAD_ARG, "blp_build_queries: a filter index needs both key arrays, index_R > 0 and all three segment outputs");
     DeviceGuard guard(device);

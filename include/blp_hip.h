@@ -482,8 +482,9 @@ int blp_topk(int model, const float *table, int64_t N, int D, int64_t ld, int64_
              size_t workspace_bytes, int device, void *stream);
 /* Merge `lists` per-query lists -- e.g. the blp_topk results of several candidate shards, gathered side by side: rows / scores
  * (Q, lists x k_in), each list of k_in slots in blp_topk's order -- into the k best per query (rows_out, scores_out (Q, k)),
- * by the same order; a row < 0 is an empty slot and sorts last.  Rows must be below 2^31.  Scores are copied (a NaN comes
- * out as the quiet NaN 0x7fc00000).  The second stage of blp_topk, on caller-given lists; no workspace. */
+ * by the same order; a row < 0 is an empty slot and sorts last.  Rows must be below 2^31.  The non-empty rows of one query
+ * are distinct (the order breaks ties by row; what a row given twice gives is not specified).  Scores are copied (a NaN
+ * comes out as the quiet NaN 0x7fc00000).  The second stage of blp_topk, on caller-given lists; no workspace. */
 int blp_topk_merge(const int64_t *rows, const float *scores, int64_t Q, int lists, int k_in, int k, int64_t *rows_out,
                    float *scores_out, int device, void *stream);
 /* blp_topk over a candidate table in any storage type (table_dtype: BLP_DTYPE_*; see "THE CANDIDATE TABLE MAY COME IN A 16-BIT
