@@ -156,8 +156,14 @@ __device__ __forceinline__ void gather_transpose(float (&x)[32], float* slab, in
     }
 }
 
+// `seen(f, r)` is called once per column with the lane's own fixed-entity and relation elements, which the routine holds in
+// registers anyway: a caller that wants something else from the query's rows (rank_sad.hip: the range of the pre-pass's
+// coefficients) gets it from this pass over them.  It has no part in the key.
+struct NothingSeen { __device__ __forceinline__ void operator()(float, float) const {} };
+
+template <class Seen = NothingSeen>
 __device__ __forceinline__ float transe_key_64_rt(const float* pe, const float* pf, const float* pr, int D, bool head,
-                                                  float* slab, int lane) {
+                                                  float* slab, int lane, Seen&& seen = Seen()) {
     const int sub_row = lane >> 3, sub_col = (lane & 7) * 4;
     const float* ge[8];
     const float* gf[8];
@@ -185,7 +191,10 @@ __device__ __forceinline__ float transe_key_64_rt(const float* pe, const float* 
         for (int k = 0; k < 32; ++k) {
             float x = (head ? e[k] : f[k]) + r[k];
             x = x - (head ? f[k] : e[k]);
-            if (k < cols) sum = sum + fabsf(x);
+            if (k < cols) {
+                sum = sum + fabsf(x);
+                seen(f[k], r[k]);
+            }
         }
     }
     return -sum;

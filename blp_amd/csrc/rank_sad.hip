@@ -28,8 +28,8 @@
 //           code that produced s_true) and counted exactly.  A workgroup whose list is short (<= kSInlineCap pairs:
 //           practically all of them on embedding-like data, ~75 pairs on average) does that itself before it exits --
 //           the gathers are all latency, which the CU's other workgroups cover with their SADs -- and writes nothing to
-//           the global list; longer lists are compacted into the global list for sad_refine_pairs_kernel, whose launch
-//           otherwise finds the list empty.  Flagged segments go to sad_refine_tiles_kernel.
+//           the global list; longer lists are compacted into the global list for sad_refine_kernel's pair workgroups,
+//           which otherwise find the list empty.  Flagged segments go to the same launch's sweep workgroups.
 // Non-finite values anywhere, or a degenerate range, make every kernel of the pre-pass a no-op and the
 // segment refinement sweep all tiles: the result is exact in every case, just slower.
 #include <hip/hip_runtime.h>
@@ -49,23 +49,42 @@
 namespace blp {
 
 
+// The prelude: the true entities' keys with the zeroed accumulators, and the range of everything the call quantises, in ONE
+// launch and one pass over the queries' rows.  Workgroups [0, query_blocks): a wave takes 64 queries at a time, one lane per
+// query, through the routine of rank_all.hip's true_key_kernel (exact_coop.h: transe_key_64_rt -- the same operations in the
+// same order, so the same keys bit for bit); the routine holds the lane's fixed-entity and relation elements in registers on
+// the way, and the query's coefficients c = h + r | t - r go from there into the lane's range.  (As launches of their own
+// the keys read the rows once and the range read them again.)  The other workgroups take the table's range.  Every
+// workgroup leaves one partial result; sad_quantize_kernel's workgroups reduce them.
+constexpr int kSPreludeQueryBlocks = 768;  // at most; with the table's at most kSRangeBlocks partial results
+constexpr int kSPreludeTableBlocks = kSRangeBlocks - kSPreludeQueryBlocks;
+constexpr int kSPreludeTableItems = 8;     // float4 loads of a table workgroup's thread (while the cap allows)
+
 template <int D>
-__global__ __launch_bounds__(256) void sad_range_kernel(const float* __restrict__ table, int64_t N, int64_t ld,
-                                                        const QRows q_fixed,
-                                                        const QRows q_rel, int64_t q_head, int64_t Q,
-                                                        SadParams* __restrict__ partial) {
+__global__ __launch_bounds__(256) void sad_prelude_kernel(const float* __restrict__ table, int64_t N, int64_t ld,
+                                                          const QRows q_true, const QRows q_fixed, const QRows q_rel,
+                                                          int64_t q_head, int64_t Q, unsigned query_blocks,
+                                                          float* __restrict__ key_true, unsigned long long* __restrict__ acc,
+                                                          SadParams* __restrict__ partial) {
     SadRange range;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x, t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (int64_t i = t0; i < N * (D / 4); i += stride) {
-        const float4 v = *reinterpret_cast<const float4*>(table + (i / (D / 4)) * ld + (i % (D / 4)) * 4);
-        range.see(v.x); range.see(v.y); range.see(v.z); range.see(v.w);
-    }
-    for (int64_t u = t0; u < Q * (D / 4); u += stride) {  // four coefficients per step: one row lookup each side
-        const bool head = u / (D / 4) < q_head;
-        const float4 f = *reinterpret_cast<const float4*>(q_fixed.flat(4 * u, D));
-        const float4 r = *reinterpret_cast<const float4*>(q_rel.flat(4 * u, D));
-        range.see(sad_coef(f.x, r.x, head)); range.see(sad_coef(f.y, r.y, head));
-        range.see(sad_coef(f.z, r.z, head)); range.see(sad_coef(f.w, r.w, head));
+    if (blockIdx.x < query_blocks) {
+        __shared__ __attribute__((aligned(16))) float slab[4][64 * kRefStride];
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        const int64_t n_groups = (Q + 63) / 64;
+        for (int64_t g = (int64_t)blockIdx.x * 4 + wave; g < n_groups; g += (int64_t)query_blocks * 4) {  // wave-uniform
+            const bool live = g * 64 + lane < Q;
+            const int64_t q = live ? g * 64 + lane : Q - 1;
+            const bool head = q < q_head;
+            auto seen = [&](float f, float r) { if (live) range.see(sad_coef(f, r, head)); };
+            const float key = transe_key_64_rt(q_true.row(q), q_fixed.row(q), q_rel.row(q), D, head, slab[wave], lane, seen);
+            if (live) { key_true[q] = key; acc[q] = 0; }
+        }
+    } else {
+        const int64_t stride = (int64_t)(gridDim.x - query_blocks) * 256;
+        for (int64_t i = (int64_t)(blockIdx.x - query_blocks) * 256 + threadIdx.x; i < N * (D / 4); i += stride) {
+            const float4 v = *reinterpret_cast<const float4*>(table + (i / (D / 4)) * ld + (i % (D / 4)) * 4);
+            range.see(v.x); range.see(v.y); range.see(v.z); range.see(v.w);
+        }
     }
     sad_range_block_store(range, partial);
 }
@@ -73,9 +92,6 @@ __global__ __launch_bounds__(256) void sad_range_kernel(const float* __restrict_
 // Candidate tile image: 64 rows per tile, uint4 index ((tile * D/8 + j4) * 64 + lane) holds dwords
 // 4 j4 .. 4 j4 + 3 of row (tile * 64 + lane); dword j packs elements 2j (low half) and 2j + 1.
 // resid[row] = the row's rounding residual E_c, rounded up to an integer.
-constexpr int64_t kSFoldFinishBlocks = 1024;  // quantising workgroups up to which they finish the range themselves ...
-constexpr int64_t kSFoldRangeBlocks = 256;    // ... from at most this many partial results
-
 template <int D>
 __device__ __forceinline__ void sad_quantize_table_tile(int64_t tile, const float* __restrict__ table, int64_t N,
                                                         int64_t ld, const SadParams* __restrict__ p,
@@ -114,8 +130,15 @@ __device__ __forceinline__ void sad_quantize_table_tile(int64_t tile, const floa
 }
 
 // Query image (D/2 dwords per query, same packing) and the two signed thresholds {T_lo, T_hi}.
-// D/2 consecutive threads per query (32, 64 or 128: whole waves or half-waves).
+// D/8 consecutive threads per query (8, 16 or 32: part of one wave), 8 consecutive coefficients per thread: two float4 loads
+// each of the fixed-entity and the relation row, one uint4 store of the image.  A workgroup takes kSQuantPasses x 256 / (D/8)
+// consecutive queries, 256 / (D/8) per pass.
+// The residual E_q is summed in f32 in a fixed order: a thread adds its 8 elements' residuals in element order, then the
+// query's D/8 threads are combined pairwise by an xor butterfly (lane distance 1, 2, 4, ...).  Another order than summing
+// the elements left to right rounds differently in the last bits, which is why the band takes the sum times 1.0001 plus
+// kSResidSlack per element: the thresholds stay rigorous whatever the order.
 // (workgroup vblock of vgrid)
+constexpr int kSQuantPasses = 4;
 template <int D>
 __device__ __forceinline__ void sad_quantize_queries_block(int64_t vblock, int64_t vgrid, const QRows& q_fixed,
                                                            const QRows& q_rel, int64_t q_head,
@@ -124,60 +147,61 @@ __device__ __forceinline__ void sad_quantize_queries_block(int64_t vblock, int64
                                                            unsigned* __restrict__ qimg,
                                                            int2* __restrict__ thr, unsigned* __restrict__ flags,
                                                            int64_t n_flag_words) {
-    const int64_t i = vblock * 256 + threadIdx.x;
-    for (int64_t j = i; j < n_flag_words; j += vgrid * 256) flags[j] = 0;  // first slab's bitmap
+    for (int64_t j = vblock * 256 + threadIdx.x; j < n_flag_words; j += vgrid * 256) flags[j] = 0;  // first slab's bitmap
     const SadScale sc = sad_scale(p);
     if (!sc.ok) return;
-    __shared__ float part_res[4], part_max[4];
-    __shared__ int part_out[4];
-    const bool live = i < Q * (D / 2);
-    const int64_t q = live ? i / (D / 2) : Q - 1;
-    const bool head = q < q_head;
-    float res = 0.f, qmax = 0.f;  // qmax: the query's largest |fixed|, |rel| (its share of the rounding term rho)
-    bool outside = false;         // a coefficient the map does not cover: the query is left to the exact path
-    if (live) {
-        const float2 f = *reinterpret_cast<const float2*>(q_fixed.flat(2 * i, D));
-        const float2 r = *reinterpret_cast<const float2*>(q_rel.flat(2 * i, D));
-        unsigned w = sad_quant(sad_coef(f.x, r.x, head), sc, res, outside);
-        w |= sad_quant(sad_coef(f.y, r.y, head), sc, res, outside) << 16;
-        qimg[i] = w;
-        qmax = fmaxf(fmaxf(fabsf(f.x), fabsf(f.y)), fmaxf(fabsf(r.x), fabsf(r.y)));  // (NaN: outside is set anyway)
-    }
+    constexpr int TQ = D / 8;  // threads per query
+    const int part = threadIdx.x % TQ;
 #pragma unroll
-    for (int off = 1; off < (D / 2 < 64 ? D / 2 : 64); off <<= 1) {
-        res += __shfl_xor(res, off);
-        qmax = fmaxf(qmax, __shfl_xor(qmax, off));
-        outside |= (bool)__shfl_xor((int)outside, off);
-    }
-    if constexpr (D / 2 > 64) {  // D = 256: two waves per query
-        const int w = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) { part_res[w] = res; part_max[w] = qmax; part_out[w] = outside; }
-        __syncthreads();
-        res = part_res[w & ~1] + part_res[w | 1];
-        qmax = fmaxf(part_max[w & ~1], part_max[w | 1]);
-        outside = part_out[w & ~1] || part_out[w | 1];
-    }
-    if (live && i % (D / 2) == 0) {
-        const double u = 5.9604644775390625e-8;
-        const double dt = -(double)key_true[q], s = (double)sc.scale;
-        const double M = (double)fmaxf(sad_range_maxabs(sc), qmax);  // every value a decided pair of this query involves
-        const double band = (double)res * 1.0001 + 2.0 * kSResidSlack * D + 1.0;  // E_q + both sides' slack
-        const double gamma = 1.05 * (D + 2) * u, rho = 6.0 * D * u * M;
-        int t_lo = -1, t_hi = (int)kSThrMax;  // nothing decided
-        if (!outside && M < 3.0e38 && dt >= 0.0 && dt < 1.0e300) {  // false for NaN
-            const double lo_v = s * (dt - rho) / (1.0 + gamma) - band;   // SAD + E_c below this: certainly above
-            const double hi_v = s * (dt + rho) / (1.0 - gamma) + band;   // SAD - E_c above this: certainly below
-            if (lo_v > 2.0) t_lo = lo_v - 1.0 < (double)kSThrMax ? (int)(lo_v - 1.0) : (int)kSThrMax;
-            if (hi_v + 2.0 < (double)kSThrMax) t_hi = (int)(hi_v + 2.0);
+    for (int pass = 0; pass < kSQuantPasses; ++pass) {  // workgroup-uniform: idle threads take the last query along, storing nothing
+        const int64_t qq = (vblock * kSQuantPasses + pass) * (256 / TQ) + threadIdx.x / TQ;
+        const bool live = qq < Q;
+        const int64_t q = live ? qq : Q - 1;
+        const bool head = q < q_head;
+        float res = 0.f;
+        bool outside = false;  // a coefficient the map does not cover: the query is left to the exact path
+        const float* fp = q_fixed.row(q) + 8 * part;
+        const float* rp = q_rel.row(q) + 8 * part;
+        const float4 f0 = *reinterpret_cast<const float4*>(fp), f1 = *reinterpret_cast<const float4*>(fp + 4);
+        const float4 r0 = *reinterpret_cast<const float4*>(rp), r1 = *reinterpret_cast<const float4*>(rp + 4);
+        const float f[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w}, r[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+        unsigned w[4];
+        float qmax = 0.f;  // the query's largest |fixed|, |rel| (its share of the rounding term rho; NaN: outside is set anyway)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            w[k] = sad_quant(sad_coef(f[2 * k], r[2 * k], head), sc, res, outside);
+            w[k] |= sad_quant(sad_coef(f[2 * k + 1], r[2 * k + 1], head), sc, res, outside) << 16;
+            qmax = fmaxf(qmax, fmaxf(fmaxf(fabsf(f[2 * k]), fabsf(f[2 * k + 1])), fmaxf(fabsf(r[2 * k]), fabsf(r[2 * k + 1]))));
         }
-        thr[q] = make_int2(t_lo, t_hi);
+        if (live) reinterpret_cast<uint4*>(qimg + q * (D / 2))[part] = make_uint4(w[0], w[1], w[2], w[3]);
+#pragma unroll
+        for (int off = 1; off < TQ; off <<= 1) {
+            res += __shfl_xor(res, off);
+            qmax = fmaxf(qmax, __shfl_xor(qmax, off));
+            outside |= (bool)__shfl_xor((int)outside, off);
+        }
+        if (live && part == 0) {
+            const double u = 5.9604644775390625e-8;
+            const double dt = -(double)key_true[q], s = (double)sc.scale;
+            const double M = (double)fmaxf(sad_range_maxabs(sc), qmax);  // every value a decided pair of this query involves
+            const double band = (double)res * 1.0001 + 2.0 * kSResidSlack * D + 1.0;  // E_q + both sides' slack
+            const double gamma = 1.05 * (D + 2) * u, rho = 6.0 * D * u * M;
+            int t_lo = -1, t_hi = (int)kSThrMax;  // nothing decided
+            if (!outside && M < 3.0e38 && dt >= 0.0 && dt < 1.0e300) {  // false for NaN
+                const double lo_v = s * (dt - rho) / (1.0 + gamma) - band;   // SAD + E_c below this: certainly above
+                const double hi_v = s * (dt + rho) / (1.0 - gamma) + band;   // SAD - E_c above this: certainly below
+                if (lo_v > 2.0) t_lo = lo_v - 1.0 < (double)kSThrMax ? (int)(lo_v - 1.0) : (int)kSThrMax;
+                if (hi_v + 2.0 < (double)kSThrMax) t_hi = (int)(hi_v + 2.0);
+            }
+            thr[q] = make_int2(t_lo, t_hi);
+        }
     }
 }
 
-// Both images in one launch: workgroups [0, table_blocks) a candidate tile each, the rest the queries.  n_partial > 0
-// (small calls: a few hundred workgroups): every workgroup first reduces the range pass's partial results itself -- in
-// the fixed order of sad_range_finish_wave, so all of them quantise with the same map -- instead of waiting for a launch of
-// its own to do it once; workgroup 0 leaves the result in *p for the kernels that follow.
+// Both images in one launch: workgroups [0, table_blocks) a candidate tile each, the rest the queries.  Every workgroup first
+// reduces the prelude's n_partial partial results itself -- in the fixed order of sad_range_finish_block, so all of them
+// quantise with the same map -- instead of waiting for a launch of its own to do it once; workgroup 0 leaves the result in
+// *p for the kernels that follow.
 template <int D>
 __global__ __launch_bounds__(256) void sad_quantize_kernel(const float* __restrict__ table, int64_t N, int64_t ld,
                                                            SadParams* __restrict__ p, const SadParams* __restrict__ partial,
@@ -188,23 +212,13 @@ __global__ __launch_bounds__(256) void sad_quantize_kernel(const float* __restri
                                                            int2* __restrict__ thr, unsigned* __restrict__ flags,
                                                            int64_t n_flag_words) {
     __shared__ SadParams p_block;
-    const SadParams* pp = p;
-    if (n_partial > 0) {
-        if (threadIdx.x < 64) {
-            const SadParams r = sad_range_finish_wave(partial, n_partial, threadIdx.x);
-            if (threadIdx.x == 0) {
-                p_block = r;
-                if (blockIdx.x == 0) *p = r;
-            }
-        }
-        __syncthreads();
-        pp = &p_block;
-    }
+    sad_range_finish_block(partial, n_partial, &p_block);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *p = p_block;
     if (blockIdx.x < table_blocks)
-        sad_quantize_table_tile<D>(blockIdx.x, table, N, ld, pp, cimg, resid);
+        sad_quantize_table_tile<D>(blockIdx.x, table, N, ld, &p_block, cimg, resid);
     else
-        sad_quantize_queries_block<D>(blockIdx.x - table_blocks, gridDim.x - table_blocks, q_fixed, q_rel, q_head, Q, key_true, pp,
-                                      qimg, thr, flags, n_flag_words);
+        sad_quantize_queries_block<D>(blockIdx.x - table_blocks, gridDim.x - table_blocks, q_fixed, q_rel, q_head, Q, key_true,
+                                      &p_block, qimg, thr, flags, n_flag_words);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -408,7 +422,7 @@ __global__ __launch_bounds__(kSW * 64, (TPW * D / 2 <= 64 ? 5 : TPW * D / 2 <= 1
     if (total <= kSInlineCap) {
         // A short list is refined here, by wave 0, 64 pooled pairs per trip, instead of going through the global list and a
         // launch of its own: the trip is all latency (three gathered 512-byte rows per pair, ~2 % of the pre-pass's VALU
-        // work), and the CU's other workgroups keep the SAD pipe busy meanwhile.  Same keys as sad_refine_pairs_kernel,
+        // work), and the CU's other workgroups keep the SAD pipe busy meanwhile.  Same keys as sad_refine_pairs_role,
         // bit for bit; rows are slab-relative, like the list's.  Nothing is written to the list, no space reserved in it.
         // (When the gate says heavy, fallback_prep zeroes acc after this kernel: what is added here is recounted.)
         if (wave == 0) {
@@ -425,7 +439,7 @@ __global__ __launch_bounds__(kSW * 64, (TPW * D / 2 <= 64 ? 5 : TPW * D / 2 <= 1
                 if (gt | ge_) atomicAdd(acc + q, gt | (ge_ << 32));
             }
         }
-    } else {  // a long one: compacted into the global list for sad_refine_pairs_kernel
+    } else {  // a long one: compacted into the global list for sad_refine_kernel
         if (tid == 0) {
             const unsigned base = atomicAdd(&params->n_pairs, total);
             for (int w = 0; w < kSW; ++w) wave_base[w] = base + start[w];
@@ -451,18 +465,14 @@ __global__ __launch_bounds__(kSW * 64, (TPW * D / 2 <= 64 ? 5 : TPW * D / 2 <= 1
 // time, and transposes them through a wave-private LDS slab so that lane p ends up with row p; the rows are
 // gathered through per-lane pointers instead of being consecutive.  Same arithmetic as Scorer<TRANSE, *, D>::score.
 template <int D>
-__global__ __launch_bounds__(64) void sad_refine_pairs_kernel(const float* __restrict__ table, int64_t ld,
-                                                              const QRows q_fixed,
-                                                              const QRows q_rel,
-                                                              const float* __restrict__ key_true, int64_t q_head,
-                                                              const uint2* __restrict__ pairs,
-                                                              const SadParams* __restrict__ params,
-                                                              unsigned long long* __restrict__ acc, const Gate gate) {
-    if (gate_heavy(gate)) return;  // the lists ran full: the exact kernel re-ranks the block (rank_common.h: Gate)
-    __shared__ __attribute__((aligned(16))) float slab[64 * kRefStride];
-    const int lane = threadIdx.x;
+__device__ __forceinline__ void sad_refine_pairs_role(int64_t wave_id, int64_t n_waves, float* slab, const float* __restrict__ table,
+                                                      int64_t ld, const QRows& q_fixed, const QRows& q_rel,
+                                                      const float* __restrict__ key_true, int64_t q_head,
+                                                      const uint2* __restrict__ pairs, const SadParams* __restrict__ params,
+                                                      unsigned long long* __restrict__ acc) {
+    const int lane = threadIdx.x & 63;
     const int64_t n = params->n_pairs;
-    for (int64_t base = (int64_t)blockIdx.x * 64; base < n; base += (int64_t)gridDim.x * 64) {  // wave-uniform
+    for (int64_t base = wave_id * 64; base < n; base += n_waves * 64) {  // wave-uniform
         const int64_t i = base + lane;
         const uint2 p = i < n ? pairs[i] : make_uint2(kSNoPair, 0u);
         const bool live = p.x != kSNoPair;
@@ -478,23 +488,16 @@ __global__ __launch_bounds__(64) void sad_refine_pairs_kernel(const float* __res
 // Pass 2b: one wave per query sweeps the query's flag words; every flagged 64-candidate tile is
 // re-scored exactly.  When the pre-pass did not run (non-finite input, degenerate range) all tiles are.
 template <int D>
-__global__ __launch_bounds__(256) void sad_refine_tiles_kernel(const float* __restrict__ table, int64_t n_rows,
-                                                               int64_t ld, const QRows q_fixed,
-                                                               const QRows q_rel,
-                                                               const float* __restrict__ key_true, int64_t q_head,
-                                                               int64_t Q, int words_per_query,
-                                                               const unsigned* __restrict__ flags,
-                                                               const SadParams* __restrict__ params,
-                                                               unsigned long long* __restrict__ acc, const Gate gate,
-                                                               const FallbackPrep prep, int64_t q_tail) {
-    if (gate_heavy(gate)) {  // the lists ran full: the exact kernel re-ranks the block (rank_common.h: Gate); this grid prepares it
-        fallback_prep<TRANSE, D>(prep, q_fixed, q_rel, q_head, q_tail);
-        return;
-    }
+__device__ __forceinline__ void sad_refine_tiles_role(int64_t vblock, const float* __restrict__ table, int64_t n_rows,
+                                                      int64_t ld, const QRows& q_fixed, const QRows& q_rel,
+                                                      const float* __restrict__ key_true, int64_t q_head,
+                                                      int64_t Q, int words_per_query, const unsigned* __restrict__ flags,
+                                                      const SadParams* __restrict__ params,
+                                                      unsigned long long* __restrict__ acc) {
     __shared__ int list[kSweepQueries], n_list;
     const bool all = !sad_scale(params).ok;
     const int lane = threadIdx.x & 63;
-    const int64_t q_base = (int64_t)blockIdx.x * kSweepQueries;
+    const int64_t q_base = vblock * kSweepQueries;
     const int n = flagged_queries(flags, q_base, Q, words_per_query, all, list, &n_list);
     for (int i = threadIdx.x >> 6; i < n; i += 4) {
     const int64_t q = q_base + list[i];
@@ -533,6 +536,33 @@ __global__ __launch_bounds__(256) void sad_refine_tiles_kernel(const float* __re
         ge += __shfl_down(ge, off);
     }
     if (lane == 0) atomicAdd(acc + q, (unsigned long long)gt | ((unsigned long long)ge << 32));
+    }
+}
+
+// Pass 2 as ONE launch: workgroups [0, pair_blocks) take the listed pairs (each of the four waves its own slab and its own
+// 64 pairs per trip), the others sweep the flags, kSweepQueries queries each.  On embedding-like data both find nothing to
+// do, and a launch that finds nothing costs what it costs to start: one of them instead of two.
+template <int D>
+__global__ __launch_bounds__(256) void sad_refine_kernel(const float* __restrict__ table, int64_t n_rows, int64_t ld,
+                                                         const QRows q_fixed, const QRows q_rel,
+                                                         const float* __restrict__ key_true, int64_t q_head, int64_t Q,
+                                                         unsigned pair_blocks, const uint2* __restrict__ pairs,
+                                                         int words_per_query, const unsigned* __restrict__ flags,
+                                                         const SadParams* __restrict__ params,
+                                                         unsigned long long* __restrict__ acc, const Gate gate,
+                                                         const FallbackPrep prep, int64_t q_tail) {
+    if (gate_heavy(gate)) {  // the lists ran full: the exact kernel re-ranks the block (rank_common.h: Gate); this grid prepares it
+        fallback_prep<TRANSE, D>(prep, q_fixed, q_rel, q_head, q_tail);
+        return;
+    }
+    if (blockIdx.x < pair_blocks) {
+        __shared__ __attribute__((aligned(16))) float slab[4][64 * kRefStride];
+        const int wave = threadIdx.x >> 6;
+        sad_refine_pairs_role<D>((int64_t)blockIdx.x * 4 + wave, (int64_t)pair_blocks * 4, slab[wave], table, ld, q_fixed, q_rel,
+                                 key_true, q_head, pairs, params, acc);
+    } else {
+        sad_refine_tiles_role<D>(blockIdx.x - pair_blocks, table, n_rows, ld, q_fixed, q_rel, key_true, q_head, Q, words_per_query,
+                                 flags, params, acc);
     }
 }
 
@@ -623,7 +653,7 @@ static SadWorkspace carve_sad(void* base, int D, int64_t N, int64_t q_head, int6
     return w;
 }
 
-// Worth it once its longer launch chain (range, quantisation, pre-pass, two refinement kernels: 8 launches against
+// Worth it once its longer launch chain (prelude, quantisation, pre-pass, refinement, gated fall-back: 6 launches against
 // the exact path's 4) is paid for by the 2.3x cheaper pair-element: measured on the FB15k-237 table (14 541 rows) the
 // exact f32 kernels win up to ~256 queries (128 queries: 42 vs 59 us), on the 4.6 M-row table the pre-pass wins from 64
 // queries on -- i.e. from about 4 million (query, candidate) pairs (tools/bench_small_blocks.py).
@@ -667,31 +697,26 @@ static hipError_t rank_sad_impl(const float* table, int64_t N, int64_t ld, const
     constexpr int TPW = sad_tiles_per_wave(D);
     const int64_t Q = q_head + q_tail;
     SadWorkspace w = carve_sad(workspace, D, N, q_head, q_tail);
-    // (the true keys of a small call folded into the range launch, one lane per query: tried -- 2 us slower from 256
-    //  queries on, where this path starts)
-    hipError_t err = launch_true_keys(TRANSE, D, q_fixed, q_rel, q_head, q_tail, q_true, w.key_true, w.acc,
-                                      stream);
-    if (err != hipSuccess) return err;
-    if (ev_start) (void)hipEventRecord(ev_start, stream);
+    hipError_t err = hipSuccess;
+    if (ev_start) (void)hipEventRecord(ev_start, stream);  // before the prelude: the timed span covers the true keys as well
     const int64_t n_tiles = (N + 63) / 64;
-    const int64_t query_blocks = (Q * (D / 2) + 255) / 256;
+    const int64_t queries_per_block = kSQuantPasses * 256 / (D / 8);
+    const int64_t query_blocks = (Q + queries_per_block - 1) / queries_per_block;
     if (n_tiles + query_blocks > 0x7fffffff) return hipErrorInvalidValue;
-    // small calls: no launch for the range's last step -- the quantising workgroups do it themselves (from fewer partials)
-    const bool fold_finish = n_tiles + query_blocks <= kSFoldFinishBlocks;
-    int64_t range_blocks;
-    {
-        const int64_t items = N * (D / 4) > Q * D ? N * (D / 4) : Q * D, cap = fold_finish ? kSFoldRangeBlocks : kSRangeBlocks;
-        range_blocks = (items + 255) / 256;
-        range_blocks = range_blocks < cap ? (range_blocks > 0 ? range_blocks : 1) : cap;
-        sad_range_kernel<D><<<dim3((unsigned)range_blocks), 256, 0, stream>>>(table, N, ld, q_fixed, q_rel, q_head, Q, w.partial);
-        if (!fold_finish) sad_range_finish_kernel<<<1, 64, 0, stream>>>(w.partial, (int)range_blocks, w.params);
-    }
+    // the prelude's grid: a wave per 64 queries and kSPreludeTableItems float4 per thread of the table, each side up to its
+    // share of the kSRangeBlocks partial results (beyond: the workgroups stride)
+    int64_t key_blocks = ((Q + 63) / 64 + 3) / 4, range_blocks = (N * (D / 4) + 256 * kSPreludeTableItems - 1) / (256 * kSPreludeTableItems);
+    key_blocks = key_blocks < kSPreludeQueryBlocks ? key_blocks : kSPreludeQueryBlocks;
+    range_blocks = range_blocks < kSPreludeTableBlocks ? (range_blocks > 0 ? range_blocks : 1) : kSPreludeTableBlocks;
+    const int n_partial = (int)(key_blocks + range_blocks);
+    sad_prelude_kernel<D><<<dim3((unsigned)n_partial), 256, 0, stream>>>(table, N, ld, q_true, q_fixed, q_rel, q_head, Q,
+                                                                         (unsigned)key_blocks, w.key_true, w.acc, w.partial);
     // the first slab's flag bitmap and pair counter are zeroed by the prep kernels (later slabs: memsets)
     const int64_t first_rows = N < w.pass_groups * kSW * TPW * 64 ? N : w.pass_groups * kSW * TPW * 64;
     const int64_t first_groups = ((first_rows + 63) / 64 + kSW * TPW - 1) / (kSW * TPW);
     const int64_t first_words = (first_groups * kSW * TPW + 31) / 32;
     sad_quantize_kernel<D><<<dim3((unsigned)(n_tiles + query_blocks)), 256, 0, stream>>>(
-        table, N, ld, w.params, w.partial, fold_finish ? (int)range_blocks : 0, w.cimg, w.resid, (unsigned)n_tiles, q_fixed, q_rel,
+        table, N, ld, w.params, w.partial, n_partial, w.cimg, w.resid, (unsigned)n_tiles, q_fixed, q_rel,
         q_head, Q, w.key_true, w.qimg, w.thr, w.flags, first_words * Q);
 
     const int64_t tiles_per_group = kSW * TPW;
@@ -715,16 +740,17 @@ static hipError_t rank_sad_impl(const float* table, int64_t N, int64_t ld, const
         rank_sad_kernel<D, TPW><<<dim3((unsigned)n_blocks), kSW * 64, 0, stream>>>(
             w.cimg + (slab0 / 64) * (D / 8) * 64, w.resid + slab0, n_rows, (int)n_groups, per_group, w.qimg, w.thr, Q, words, w.acc,
             w.flags, w.pairs, w.params, slab, ld, q_fixed, q_rel, q_head, w.key_true);
-        const int64_t pair_blocks = (n_blocks * kSQuota + 63) / 64;  // 64 pairs per single-wave workgroup and iteration
+        // the pair role: 64 pairs per wave and trip, four waves per workgroup, up to 10 workgroups per compute unit
+        int64_t pair_blocks = (n_blocks * kSQuota + 255) / 256;
+        pair_blocks = pair_blocks < (int64_t)n_cu * 10 ? pair_blocks : (int64_t)n_cu * 10;
+        const int64_t sweep_blocks = (Q + kSweepQueries - 1) / kSweepQueries;
         // heavy <=> the workgroups' lists are >= 90 % full (capacity: kSQuota entries each): exact ties on whole percents of the
         // table -- the flagged tiles would then cost 64 exact scores per flag (132 ms for the FB15k-237 block at 5 % ties) where
         // the exact kernel re-ranks everything in 8
         const Gate gate{w.fallback_coef ? &w.params->n_listed : nullptr, (unsigned)((n_blocks * kSQuota / 10 * 9) < 0xffffffffll ? n_blocks * kSQuota / 10 * 9 : 0xffffffffll)};
-        sad_refine_pairs_kernel<D><<<dim3((unsigned)(pair_blocks < (int64_t)n_cu * 40 ? pair_blocks : (int64_t)n_cu * 40)), 64, 0, stream>>>(
-            slab, ld, q_fixed, q_rel, w.key_true, q_head, w.pairs, w.params, w.acc, gate);
-        sad_refine_tiles_kernel<D><<<dim3((unsigned)((Q + kSweepQueries - 1) / kSweepQueries)), 256, 0, stream>>>(
-            slab, n_rows, ld, q_fixed, q_rel, w.key_true, q_head, Q, words, w.flags, w.params, w.acc, gate,
-            FallbackPrep{w.fallback_coef, w.acc}, q_tail);
+        sad_refine_kernel<D><<<dim3((unsigned)(pair_blocks + sweep_blocks)), 256, 0, stream>>>(
+            slab, n_rows, ld, q_fixed, q_rel, w.key_true, q_head, Q, (unsigned)pair_blocks, w.pairs, words, w.flags, w.params, w.acc,
+            gate, FallbackPrep{w.fallback_coef, w.acc}, q_tail);
         if (gate.counter) {
             err = launch_exact_fallback(TRANSE, D, table, N, ld, q_fixed, q_rel, q_head, q_tail, w.fallback_coef, w.key_true, w.acc, gate,
                                         n_cu, stream);

@@ -118,6 +118,21 @@ __device__ __forceinline__ void sad_range_block_store(SadRange r, SadParams* __r
     }
 }
 
+// The final record from the reduced range: counters cleared, the range clamped to mean +- kSClampSigmas standard deviations
+__device__ __forceinline__ SadParams sad_range_final(const SadRange& r) {
+    SadParams p = r.record();
+    p.n_pairs = p.n_listed = 0;
+    if (r.count > 0 && r.lo <= r.hi) {
+        const double mean = r.sum / (double)r.count;
+        const double var = r.sumsq / (double)r.count - mean * mean;
+        const double sd = var > 0.0 ? sqrt(var) : 0.0;
+        const float lo_c = (float)(mean - kSClampSigmas * sd), hi_c = (float)(mean + kSClampSigmas * sd);
+        if (lo_c > ord2f(r.lo)) p.lo_ord = f2ord(lo_c);
+        if (hi_c < ord2f(r.hi)) p.hi_ord = f2ord(hi_c);
+    }
+    return p;
+}
+
 // The range of the whole input from the n partial results, by one wave (fixed order: every caller gets the same bits);
 // the result is valid on lane 0.
 __device__ __forceinline__ SadParams sad_range_finish_wave(const SadParams* __restrict__ partial, int n, int lane) {
@@ -127,17 +142,37 @@ __device__ __forceinline__ SadParams sad_range_finish_wave(const SadParams* __re
         r.merge(p.lo_ord, p.hi_ord, p.nonfinite, p.sum, p.sumsq, p.count);
     }
     r.wave_reduce();
-    SadParams p = r.record();
-    p.n_pairs = p.n_listed = 0;
-    if (r.count > 0 && r.lo <= r.hi) {  // clamp the range to mean +- kSClampSigmas standard deviations
-        const double mean = r.sum / (double)r.count;
-        const double var = r.sumsq / (double)r.count - mean * mean;
-        const double sd = var > 0.0 ? sqrt(var) : 0.0;
-        const float lo_c = (float)(mean - kSClampSigmas * sd), hi_c = (float)(mean + kSClampSigmas * sd);
-        if (lo_c > ord2f(r.lo)) p.lo_ord = f2ord(lo_c);
-        if (hi_c < ord2f(r.hi)) p.hi_ord = f2ord(hi_c);
+    return sad_range_final(r);
+}
+
+// The same by a whole 256-thread workgroup from n <= kSRangeBlocks partial results: thread t takes records t, t + 256, ...
+// (at most four loads, all in flight together: one trip to memory, where one wave would make up to sixteen in turn), then
+// wave_reduce and the four waves' results in order.  A fixed order again: every workgroup of a grid computes the same bits,
+// which is what lets each of them finish the range for itself instead of waiting for a launch that does it once.  The result
+// is in *out (shared memory) for all threads after the call.
+__device__ __forceinline__ void sad_range_finish_block(const SadParams* __restrict__ partial, int n, SadParams* out) {
+    __shared__ SadParams part[4];
+    static_assert(kSRangeBlocks <= 4 * 256, "four records per thread");
+    SadParams rec[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = k * 256 + (int)threadIdx.x;
+        rec[k] = partial[i < n ? i : 0];
     }
-    return p;
+    SadRange r;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k * 256 + (int)threadIdx.x < n)
+            r.merge(rec[k].lo_ord, rec[k].hi_ord, rec[k].nonfinite, rec[k].sum, rec[k].sumsq, rec[k].count);
+    r.wave_reduce();
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = r.record();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        SadRange t;
+        for (int w = 0; w < 4; ++w) t.merge(part[w].lo_ord, part[w].hi_ord, part[w].nonfinite, part[w].sum, part[w].sumsq, part[w].count);
+        *out = sad_range_final(t);
+    }
+    __syncthreads();
 }
 
 static __global__ __launch_bounds__(64) void sad_range_finish_kernel(const SadParams* __restrict__ partial, int n,
