@@ -22,6 +22,7 @@ STATUS_NAMES = {0: "BLP_OK", -1: "BLP_ERR_BAD_ARG", -2: "BLP_ERR_UNSUPPORTED_DIM
 # every symbol include/blp_hip.h declares (tests check the .so exports exactly these)
 SYMBOLS = ("blp_version", "blp_last_error", "blp_device_caps", "blp_selftest", "blp_dim_supported",
            "blp_rank_all_workspace_bytes", "blp_rank_all_supported", "blp_rank_all", "blp_rank_all_shard", "blp_gather_triple_vectors",
+           "blp_rank_all_wide_supported", "blp_rank_all_wide_workspace_bytes", "blp_rank_all_wide",
            "blp_rank_all_batches", "blp_rank_all_batches_workspace_bytes", "blp_rank_all_batches_passes_per_launch",
            "blp_rank_all_batches_native16", "blp_profile_next_rank_kernel", "blp_rank_all_prepass_stats", "blp_rank_from_scores",
            "blp_rank_metrics", "blp_rank_metric_sums", "blp_score_fwd", "blp_score_bwd", "blp_inbatch_loss_save_floats",
@@ -154,6 +155,13 @@ def _load(path, hooks):
     L.blp_rank_all.restype = _i
     L.blp_rank_all.argtypes = [_i, _vp, _i64, _i, _i64, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.POINTER(BlpFilter),
                                _vp, _vp, _sz, _i, _vp]
+    L.blp_rank_all_wide_supported.restype = _i
+    L.blp_rank_all_wide_supported.argtypes = [_i, _i]
+    L.blp_rank_all_wide_workspace_bytes.restype = _sz
+    L.blp_rank_all_wide_workspace_bytes.argtypes = [_i, _i64, _i, _i64, _i64]
+    L.blp_rank_all_wide.restype = _i
+    L.blp_rank_all_wide.argtypes = [_i, _vp, _i64, _i, _i64, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.POINTER(BlpFilter),
+                                    _vp, _vp, _sz, _i, _vp]
     L.blp_rank_all_shard.restype = _i
     L.blp_rank_all_shard.argtypes = [_i, _vp, _i64, _i, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64,
                                      ctypes.POINTER(BlpFilter), _vp, _vp, _sz, _i, _vp]

@@ -301,45 +301,48 @@ size_t blp_rank_all_workspace_bytes(int model, int64_t N, int D, int64_t q_head,
 
 }  // extern "C"
 
-// Shared by blp_rank_all (dense query vectors) and blp_rank_all_shard (queries as rows of `source` / of rel_emb)
-static int rank_all_checked(int model, const float* table, int64_t N, int D, int64_t ld, const blp::QRows& q_fixed,
+// Shared by blp_rank_all (dense query vectors), blp_rank_all_shard (queries as rows of `source` / of rel_emb) and -- wide -- by
+// blp_rank_all_wide (rank_all_wide.hip): the argument checks (messages under the entry's name `who`), then the launch
+static int rank_all_checked(const char* who, bool wide, int model, const float* table, int64_t N, int D, int64_t ld, const blp::QRows& q_fixed,
                             const blp::QRows& q_rel, const blp::QRows& q_true,
                             int64_t q_head, int64_t q_tail, const blp_filter* filter, int32_t* counts, void* workspace,
                             size_t workspace_bytes, int device, void* stream) {
-    if (!valid_model(model)) return fail(BLP_ERR_BAD_ARG, "blp_rank_all: unknown model %d", model);
-    if (!blp_rank_all_supported(model, D, q_head, q_tail))
-        return fail(BLP_ERR_UNSUPPORTED_DIM,
-                    "blp_rank_all: D = %d not supported for this block (64 / 128 / 256 always; TransE at any "
-                    "D %% 4 == 0 up to 1024): see blp_rank_all_supported", D);
+    if (!valid_model(model)) return fail(BLP_ERR_BAD_ARG, "%s: unknown model %d", who, model);
+    if (wide && !blp_rank_all_wide_supported(model, D))
+        return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: model %d at D = %d not supported (distmult / complex / simple, D %% 4 == 0, "
+                    "4 <= D <= 1024: see blp_rank_all_wide_supported)", who, model, D);
+    if (!wide && !blp_rank_all_supported(model, D, q_head, q_tail))
+        return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported for this block (64 / 128 / 256 always; TransE at any "
+                    "D %% 4 == 0 up to 1024): see blp_rank_all_supported", who, D);
     if (N < 0 || q_head < 0 || q_tail < 0 || ld < D)
-        return fail(BLP_ERR_BAD_ARG, "blp_rank_all: negative size or ld < D (N=%lld q_head=%lld q_tail=%lld ld=%lld)",
+        return fail(BLP_ERR_BAD_ARG, "%s: negative size or ld < D (N=%lld q_head=%lld q_tail=%lld ld=%lld)", who,
                     (long long)N, (long long)q_head, (long long)q_tail, (long long)ld);
     const int64_t Q = q_head + q_tail;
     if (Q == 0) return BLP_OK;
     // counts are int32, the two accumulators of a query share one 64-bit word and pair lists hold 32-bit rows
     if (Q > (1ll << 30) || N >= (1ll << 31))
-        return fail(BLP_ERR_BAD_ARG, "blp_rank_all: Q > 2^30 or N >= 2^31 (counts are int32): split the query block / "
-                                     "shard the candidate axis");
-    if (!q_fixed.base || !q_rel.base || !counts) return fail(BLP_ERR_BAD_ARG, "blp_rank_all: NULL q_fixed / q_rel / counts");
-    if (N > 0 && !table) return fail(BLP_ERR_BAD_ARG, "blp_rank_all: NULL table");
-    if (!q_true.base) return fail(BLP_ERR_BAD_ARG, "blp_rank_all: exactly one of true_row / q_true must be given");
+        return fail(BLP_ERR_BAD_ARG, "%s: Q > 2^30 or N >= 2^31 (counts are int32): split the query block / "
+                                     "shard the candidate axis", who);
+    if (!q_fixed.base || !q_rel.base || !counts) return fail(BLP_ERR_BAD_ARG, "%s: NULL q_fixed / q_rel / counts", who);
+    if (N > 0 && !table) return fail(BLP_ERR_BAD_ARG, "%s: NULL table", who);
+    if (!q_true.base) return fail(BLP_ERR_BAD_ARG, "%s: exactly one of true_row / q_true must be given", who);
     blp::FilterSpec spec;
     if (filter) {
         if (!filter->seg_lo || !filter->seg_hi || !filter->values)
-            return fail(BLP_ERR_BAD_ARG, "blp_rank_all: filter needs seg_lo, seg_hi and values");
+            return fail(BLP_ERR_BAD_ARG, "%s: filter needs seg_lo, seg_hi and values", who);
         if (filter->ent2idx && filter->ent2idx_len < 0)
-            return fail(BLP_ERR_BAD_ARG, "blp_rank_all: filter ent2idx_len is negative");
+            return fail(BLP_ERR_BAD_ARG, "%s: filter ent2idx_len is negative", who);
         spec.lo = filter->seg_lo; spec.hi = filter->seg_hi; spec.val = filter->values; spec.exclude = filter->exclude;
         spec.ent2idx = filter->ent2idx; spec.ent2idx_len = filter->ent2idx ? filter->ent2idx_len : 0;
         spec.row_base = filter->row_base;
     }
     if (!aligned16(table) || (ld & 3) || !aligned16(q_true.base) || (q_true.ld & 3) || !aligned16(counts) ||
         !aligned16(q_fixed.base) || !aligned16(q_rel.base) || (q_fixed.ld & 3) || (q_rel.ld & 3) || (D & 3))
-        return fail(BLP_ERR_BAD_ARG, "blp_rank_all: table / q_fixed / q_rel / q_true / counts must be 16-byte aligned, "
-                                     "ld %% 4 == 0 and D %% 4 == 0");
-    const size_t need = blp::rank_all_workspace_bytes(model, D, N, q_head, q_tail);
+        return fail(BLP_ERR_BAD_ARG, "%s: table / q_fixed / q_rel / q_true / counts must be 16-byte aligned, "
+                                     "ld %% 4 == 0 and D %% 4 == 0", who);
+    const size_t need = wide ? blp::rank_all_wide_workspace_bytes(q_head, q_tail) : blp::rank_all_workspace_bytes(model, D, N, q_head, q_tail);
     if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255u))
-        return fail(BLP_ERR_WORKSPACE, "blp_rank_all: workspace must be 256-byte aligned and >= %zu bytes (got %zu)",
+        return fail(BLP_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned and >= %zu bytes (got %zu)", who,
                     need, workspace_bytes);
     DeviceGuard guard(device);
     if (guard.error() != hipSuccess) return hip_fail(guard.error(), "hipSetDevice");
@@ -347,9 +350,9 @@ static int rank_all_checked(int model, const float* table, int64_t N, int D, int
     if (int rc = compute_units(device, &cu)) return rc;
     hipEvent_t ev0 = g_prof_start, ev1 = g_prof_stop;
     g_prof_start = g_prof_stop = nullptr;
-    hipError_t err = blp::launch_rank_all(model, D, table, N, ld, q_fixed, q_rel, q_true, q_head, q_tail,
-                                          spec, counts, workspace, cu, static_cast<hipStream_t>(stream), ev0, ev1);
-    if (err != hipSuccess) return hip_fail(err, "blp_rank_all launch");
+    hipError_t err = (wide ? blp::launch_rank_all_wide : blp::launch_rank_all)(model, D, table, N, ld, q_fixed, q_rel, q_true, q_head, q_tail,
+                                                                               spec, counts, workspace, cu, static_cast<hipStream_t>(stream), ev0, ev1);
+    if (err != hipSuccess) return hip_fail(err, wide ? "blp_rank_all_wide launch" : "blp_rank_all launch");
     return BLP_OK;
 }
 
@@ -362,7 +365,7 @@ int blp_rank_all(int model, const float* table, int64_t N, int D, int64_t ld, co
     blp::QRows truth;  // stays empty (-> BAD_ARG below, after the model / size checks) unless exactly one form is given
     if ((true_row == nullptr) != (q_true == nullptr))
         truth = true_row ? blp::QRows::rows_of(table, true_row, ld) : blp::QRows::dense(q_true, D);
-    return rank_all_checked(model, table, N, D, ld, blp::QRows::dense(q_fixed, D), blp::QRows::dense(q_rel, D), truth,
+    return rank_all_checked("blp_rank_all", false, model, table, N, D, ld, blp::QRows::dense(q_fixed, D), blp::QRows::dense(q_rel, D), truth,
                             q_head, q_tail, filter, counts, workspace, workspace_bytes, device, stream);
 }
 
@@ -374,10 +377,28 @@ int blp_rank_all_shard(int model, const float* table, int64_t N, int D, int64_t 
         return fail(BLP_ERR_BAD_ARG, "blp_rank_all_shard: NULL source / fixed_row / rel_id / rel_emb / true_row, or R <= 0 / S <= 0");
     if (ld_src < D || (ld_src & 3) || !aligned16(source))
         return fail(BLP_ERR_BAD_ARG, "blp_rank_all_shard: source must be 16-byte aligned with ld_src %% 4 == 0, ld_src >= D");
-    return rank_all_checked(model, table, N, D, ld, blp::QRows::rows_of(source, fixed_row, ld_src),
+    return rank_all_checked("blp_rank_all", false, model, table, N, D, ld, blp::QRows::rows_of(source, fixed_row, ld_src),
                             blp::QRows::rows_of(rel_emb, rel_id, D),
                             blp::QRows::rows_of(source, true_row, ld_src), q_head, q_tail, filter, counts, workspace,
                             workspace_bytes, device, stream);
+}
+
+// ---- the exact table pass for DistMult / ComplEx / SimplE at any width (rank_all_wide.hip): blp_rank_all's arguments, checks and codes
+int blp_rank_all_wide_supported(int model, int D) { return valid_model(model) && blp::rank_all_wide_supported(model, D) ? 1 : 0; }
+
+size_t blp_rank_all_wide_workspace_bytes(int model, int64_t N, int D, int64_t q_head, int64_t q_tail) {
+    if (!blp_rank_all_wide_supported(model, D) || N < 0 || q_head < 0 || q_tail < 0 || q_head + q_tail > (1ll << 30)) return 0;
+    return blp::rank_all_wide_workspace_bytes(q_head, q_tail);
+}
+
+int blp_rank_all_wide(int model, const float* table, int64_t N, int D, int64_t ld, const float* q_fixed, const float* q_rel,
+                      const int64_t* true_row, const float* q_true, int64_t q_head, int64_t q_tail, const blp_filter* filter,
+                      int32_t* counts, void* workspace, size_t workspace_bytes, int device, void* stream) {
+    blp::QRows truth;  // stays empty (-> BAD_ARG, after the model / size checks) unless exactly one form is given
+    if ((true_row == nullptr) != (q_true == nullptr))
+        truth = true_row ? blp::QRows::rows_of(table, true_row, ld) : blp::QRows::dense(q_true, D);
+    return rank_all_checked("blp_rank_all_wide", true, model, table, N, D, ld, blp::QRows::dense(q_fixed, D), blp::QRows::dense(q_rel, D),
+                            truth, q_head, q_tail, filter, counts, workspace, workspace_bytes, device, stream);
 }
 
 static int64_t batches_f32_passes_per_launch(int model, int64_t N, int D, int64_t ld, int64_t n_triples, int64_t batch,

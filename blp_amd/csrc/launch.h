@@ -57,6 +57,15 @@ hipError_t launch_rank_all(int model, int D, const float* table, int64_t N, int6
                            void* workspace, int n_cu, hipStream_t stream, hipEvent_t ev_start = nullptr,
                            hipEvent_t ev_stop = nullptr);
 
+// rank_all_wide.hip: the exact table pass for DistMult / ComplEx / SimplE at any width (D % 4 == 0, 4 <= D <= 1024;
+// include/blp_hip.h: blp_rank_all_wide): launch_rank_all's arguments; the workspace holds the true keys and the accumulators
+bool rank_all_wide_supported(int model, int D);
+size_t rank_all_wide_workspace_bytes(int64_t q_head, int64_t q_tail);
+hipError_t launch_rank_all_wide(int model, int D, const float* table, int64_t N, int64_t ld, const QRows q_fixed, const QRows q_rel,
+                                const QRows q_true, int64_t q_head, int64_t q_tail, const FilterSpec& filter, int32_t* counts,
+                                void* workspace, int n_cu, hipStream_t stream, hipEvent_t ev_start = nullptr,
+                                hipEvent_t ev_stop = nullptr);
+
 // rank_all.hip: many passes of <= 4 + 4 queries back to back (one preparation and one finalisation launch for all of them)
 bool rank_static_passes_applicable(int model, int D, int64_t N, int64_t batch);
 size_t rank_static_passes_workspace_bytes(int D, int64_t n, int64_t batch);

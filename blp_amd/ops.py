@@ -196,6 +196,13 @@ def rank_all(rel_model, table, q_fixed, q_rel, q_head, true_row=None, q_true=Non
     that wants to look at it afterwards: prepass_stats); default: this module's own.
     Returns counts (Q, 4) int32: gt, ge, gt_filtered, ge_filtered.
     """
+    return _rank_all_call(False, rel_model, table, q_fixed, q_rel, q_head, true_row, q_true, filt_rowptr, filt_col, out, rel_ids,
+                          filter, workspace)
+
+
+def _rank_all_call(wide, rel_model, table, q_fixed, q_rel, q_head, true_row, q_true, filt_rowptr, filt_col, out, rel_ids, filter,
+                   workspace):
+    """rank_all (blp_rank_all) and rank_all_wide (blp_rank_all_wide): the same arguments, checks and workspace cache."""
     _require_device(table, q_fixed, q_rel, true_row, q_true, filt_rowptr, filt_col, rel_ids)
     table = _f32_rows(table, "table")
     if table.dim() != 2:
@@ -239,10 +246,12 @@ def rank_all(rel_model, table, q_fixed, q_rel, q_head, true_row=None, q_true=Non
         raise ValueError("out must be a contiguous (Q, 4) int32 tensor")
     if Q == 0:
         return counts
-    ensure_selftest(dev, rel_model)
+    if not wide:
+        ensure_selftest(dev, rel_model)
     L = _lib.lib()
     model = _lib.MODEL_IDS[rel_model]
-    ws_bytes = _rank_ws_bytes(L, model, N, D, q_head, Q - q_head)
+    ws_bytes = (L.blp_rank_all_wide_workspace_bytes(model, N, D, q_head, Q - q_head) if wide
+                else _rank_ws_bytes(L, model, N, D, q_head, Q - q_head))
     stream = torch._C._cuda_getCurrentRawStream(dev.index)
     if workspace is None:
         workspace = _workspace(dev, stream, ws_bytes)
@@ -255,12 +264,32 @@ def rank_all(rel_model, table, q_fixed, q_rel, q_head, true_row=None, q_true=Non
         spec = ctypes.byref(csr)
     else:
         spec = None
-    status = L.blp_rank_all(model, table.data_ptr(), N, D, table.stride(0) if N > 0 else D, q_fixed.data_ptr(), q_rel.data_ptr(),
-                            _addr(true_row), _addr(q_true), q_head, Q - q_head, spec, counts.data_ptr(), workspace.data_ptr(),
-                            ws_bytes, dev.index, stream)
+    call = L.blp_rank_all_wide if wide else L.blp_rank_all
+    status = call(model, table.data_ptr(), N, D, table.stride(0) if N > 0 else D, q_fixed.data_ptr(), q_rel.data_ptr(),
+                  _addr(true_row), _addr(q_true), q_head, Q - q_head, spec, counts.data_ptr(), workspace.data_ptr(),
+                  ws_bytes, dev.index, stream)
     if status:
-        _lib.check(status, "blp_rank_all")
+        _lib.check(status, "blp_rank_all_wide" if wide else "blp_rank_all")
     return counts
+
+
+def rank_all_wide_supported(rel_model, dim):
+    """True if rank_all_wide takes this model and width: DistMult / ComplEx / SimplE at any D % 4 == 0, 4 <= D <= 1024
+    (include/blp_hip.h: blp_rank_all_wide_supported)."""
+    return bool(_lib.lib().blp_rank_all_wide_supported(_lib.MODEL_IDS[rel_model], int(dim)))
+
+
+def rank_all_wide(rel_model, table, q_fixed, q_rel, q_head, true_row=None, q_true=None, filt_rowptr=None, filt_col=None,
+                  filter=None, out=None, workspace=None):
+    """rank_all for DistMult / ComplEx / SimplE at any width D % 4 == 0, 4 <= D <= 1024 (the 300 / 768-wide bag-of-words and
+    DKRL tables): the exact table pass of blp_rank_all_wide, no (Q, N) score matrix.  Arguments, filter forms (CSR or
+    SegmentFilter), workspace and result as rank_all; workspace: >= rank_all_wide_workspace_bytes(...) bytes."""
+    return _rank_all_call(True, rel_model, table, q_fixed, q_rel, q_head, true_row, q_true, filt_rowptr, filt_col, out, None,
+                          filter, workspace)
+
+
+def rank_all_wide_workspace_bytes(rel_model, N, D, q_head, q_tail):
+    return int(_lib.lib().blp_rank_all_wide_workspace_bytes(_lib.MODEL_IDS[rel_model], int(N), int(D), int(q_head), int(q_tail)))
 
 
 def table16_is_read_directly(rel_model, dtype, N, D, n_triples, batch, block_triples=None, ld=None):

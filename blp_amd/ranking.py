@@ -73,6 +73,13 @@ def rank_block(model, table, q_fixed, q_rel, q_head, true_row=None, q_true=None,
     Queries [0, q_head) replace the head, the rest replace the tail (train.py:149 order).  The filter is a CSR
     (filt_rowptr, filt_col) or, on a HIP device, an ops.SegmentFilter (``filter``)."""
     if table.is_cuda and not ops.rank_all_supported(model.rel_model, table.shape[1], q_head, q_fixed.shape[0] - q_head):
+        if table.dtype is torch.float32 and ops.rank_all_wide_supported(model.rel_model, table.shape[1]):
+            # the bilinear models at any width D % 4 == 0 up to 1024: the exact table pass, either filter form
+            dev = table.device
+            return ops.rank_all_wide(model.rel_model, table, q_fixed, q_rel, q_head,
+                                     true_row=None if true_row is None else true_row.to(dev), q_true=q_true,
+                                     filt_rowptr=None if filt_rowptr is None else filt_rowptr.to(dev),
+                                     filt_col=None if filt_col is None else filt_col.to(dev), filter=filter, out=out)
         if filter is not None:
             raise ValueError("the dense any-width route takes the filter as a CSR (utils.FilterIndex.csr)")
         counts = _rank_block_generic_width(model, table, q_fixed, q_rel, q_head, true_row, q_true, filt_rowptr, filt_col)

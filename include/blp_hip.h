@@ -166,6 +166,32 @@ int blp_rank_all(int model, const float *table, int64_t N, int D, int64_t ld,
                  int64_t q_head, int64_t q_tail, const blp_filter *filter, int32_t *counts,
                  void *workspace, size_t workspace_bytes, int device, void *stream);
 
+/* ---- the same call for DistMult / ComplEx / SimplE AT ANY WIDTH: D % 4 == 0, 4 <= D <= 1024 (the 300 / 768-wide bag-of-words and
+ * DKRL encoders, models.py:118-135, 165-172, which blp_rank_all takes for TransE only).  The exact f32 pass over the table and
+ * nothing in front of it: eight lanes per candidate row restate torch's sum(dim=-1) order at run-time width from registers
+ * (rank_all_wide.hip), so the counts are the reference's bit for bit; no (Q, N) array exists anywhere.  The
+ * contract is blp_rank_all's, word for word: head queries first; exactly one of true_row / q_true; the blp_filter as segments or
+ * a CSR, with row_base, rows outside [0, N) ignored; counts (Q, 4) int32 {gt, ge, gt_filt, ge_filt}, overwritten; per-shard
+ * counts add up to the unsharded ones; asynchronous on `stream`, no allocation, no host sync; the same status codes, messages
+ * (under this entry's name) and order of checks, every check before the device is touched; Q == 0 returns BLP_OK, N == 0 gives
+ * zero counts.
+ *   blp_rank_all_wide_supported        1 for BLP_DISTMULT / BLP_COMPLEX / BLP_SIMPLE at D % 4 == 0, 4 <= D <= 1024 -- 64 / 128 /
+ *                                      256 included, where this is a second implementation of the same bits and blp_rank_all the
+ *                                      faster one --; 0 for BLP_TRANSE (blp_rank_all takes it at these widths) and anything else.
+ *                                      blp_rank_all_supported does not change.
+ *   blp_rank_all_wide_workspace_bytes  the true keys and the packed accumulators: 4 Q + 8 Q bytes, each rounded up to 256, so
+ *                                      <= 12 Q + 510 bytes (Q = q_head + q_tail), independent of N and D; 0 where the call is
+ *                                      unsupported or a size is negative.
+ *   blp_rank_all_wide                  BLP_ERR_UNSUPPORTED_DIM where blp_rank_all_wide_supported is 0.
+ * The launch chain is bounded whatever the sizes: one true-key launch, one table pass per side with a grid of at most
+ * 32 768 query chunks x 32 768 candidate slabs (workgroups stride over the chunks), one filter + finalize launch. */
+int blp_rank_all_wide_supported(int model, int D);
+size_t blp_rank_all_wide_workspace_bytes(int model, int64_t N, int D, int64_t q_head, int64_t q_tail);
+int blp_rank_all_wide(int model, const float *table, int64_t N, int D, int64_t ld,
+                      const float *q_fixed, const float *q_rel, const int64_t *true_row, const float *q_true,
+                      int64_t q_head, int64_t q_tail, const blp_filter *filter, int32_t *counts,
+                      void *workspace, size_t workspace_bytes, int device, void *stream);
+
 /* The same with the queries given as INDICES instead of vectors, for ONE SHARD OF THE CANDIDATE AXIS (the north_star's
  * multi-GPU layout: the entity table partitioned by rows over the ranks, every rank ranking every query against its own
  * rows) -- or, with source == table, for the whole table: query q's fixed-entity vector is row fixed_row[q] of `source`, its
