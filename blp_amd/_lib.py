@@ -29,6 +29,7 @@ SYMBOLS = ("blp_version", "blp_last_error", "blp_device_caps", "blp_selftest", "
            "blp_inbatch_loss_fwd_launches", "blp_inbatch_loss_fwd", "blp_inbatch_loss_bwd", "blp_project_rows_supported", "blp_project_rows", "blp_bow_rows_supported", "blp_bow_rows", "blp_dkrl_rows_supported", "blp_dkrl_rows",
            "blp_build_queries", "blp_topk_supported", "blp_topk_workspace_bytes", "blp_topk", "blp_topk_merge",
            "blp_topk_typed_supported", "blp_topk_typed_workspace_bytes", "blp_topk_typed",
+           "blp_topk_wide_supported", "blp_topk_wide_workspace_bytes", "blp_topk_wide",
            "blp_rank_lists_supported", "blp_rank_lists_workspace_bytes", "blp_rank_lists",
            "blp_rank_sets_supported", "blp_rank_sets_workspace_bytes", "blp_rank_sets",
            "blp_rank_sets_typed_supported", "blp_rank_sets_typed_workspace_bytes", "blp_rank_sets_typed",
@@ -42,7 +43,7 @@ SYMBOLS = ("blp_version", "blp_last_error", "blp_device_caps", "blp_selftest", "
            "blp_rank_relations_wide_supported", "blp_rank_relations_wide_workspace_bytes", "blp_rank_relations_wide",
            "blp_topk_relations_wide_supported", "blp_topk_relations_wide_workspace_bytes", "blp_topk_relations_wide",
            "blp_rerank_supported", "blp_rerank_cosine", "blp_rerank_ndcg")
-HOOK_SYMBOLS = ("blp_debug_set_knob", "blp_debug_gemm_dump", "blp_debug_reset_selftest")  # libblp_hip.hooks.so only
+HOOK_SYMBOLS = ("blp_debug_set_knob", "blp_debug_gemm_dump", "blp_debug_reset_selftest", "blp_debug_topk_wide_lds_bytes")  # libblp_hip.hooks.so only
 KNOBS = ("rank_kernel", "gemm_kernel", "sad_queries_per_group", "sad_pass_groups", "sad_min_queries",
          "gemm_pass_words", "gemm_tiles_per_chunk", "exact_query_chunk",
          "small_kernel", "stream_kernel", "dkrl_split", "mfma_selftest", "inbatch_probe", "inbatch_shares", "rank_sets_grid",
@@ -225,6 +226,9 @@ def _load(path, hooks):
     L.blp_topk_typed.restype = _i
     L.blp_topk_typed.argtypes = [_i, _vp, _i, _i64, _i, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i,
                                  ctypes.POINTER(BlpFilter), _vp, _vp, _vp, _sz, _i, _vp]
+    for wide, narrow in ((L.blp_topk_wide_supported, L.blp_topk_supported), (L.blp_topk_wide_workspace_bytes, L.blp_topk_workspace_bytes),
+                         (L.blp_topk_wide, L.blp_topk)):  # blp_topk's signatures, by design
+        wide.restype, wide.argtypes = narrow.restype, list(narrow.argtypes)
     L.blp_topk_merge.restype = _i
     L.blp_topk_merge.argtypes = [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _i, _vp]
     L.blp_rank_lists_supported.restype = _i
@@ -312,6 +316,8 @@ def _load(path, hooks):
         L.blp_debug_set_knob.argtypes = [ctypes.c_char_p, ctypes.c_longlong]
         L.blp_debug_reset_selftest.restype = _i
         L.blp_debug_reset_selftest.argtypes = [_i]
+        L.blp_debug_topk_wide_lds_bytes.restype = _sz
+        L.blp_debug_topk_wide_lds_bytes.argtypes = [_i, _i, _i]
     return L
 
 

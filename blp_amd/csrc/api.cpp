@@ -687,7 +687,7 @@ size_t blp_topk_workspace_bytes(int model, int64_t N, int D, int64_t q_head, int
 }
 
 // blp_topk and blp_topk_typed: the argument checks (messages under the entry's name `who`), then the launch
-static int topk_call(const char* who, int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld,
+static int topk_call(const char* who, bool wide, int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld,
                      int64_t row_base, const float* source, int64_t S, int64_t ld_src, const int64_t* fixed_row,
                      const float* rel_emb, int64_t R, const int64_t* rel_id, int64_t q_head, int64_t q_tail, int k,
                      const blp_filter* filter, int64_t* rows, float* scores, void* workspace, size_t workspace_bytes, int device,
@@ -695,7 +695,10 @@ static int topk_call(const char* who, int model, const void* table, int table_dt
     if (!valid_model(model)) return fail(BLP_ERR_BAD_ARG, "%s: unknown model %d", who, model);
     if (!valid_table_dtype(table_dtype)) return fail(BLP_ERR_BAD_ARG, "%s: unknown table dtype %d", who, table_dtype);
     if (k < 1 || k > 256) return fail(BLP_ERR_BAD_ARG, "%s: k = %d outside [1, 256]", who, k);
-    if (!blp_topk_supported(model, D, k))
+    if (wide && !blp_topk_wide_supported(model, D, k))
+        return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: model %d at D = %d not supported (distmult / complex / simple, D %% 4 == 0, "
+                    "4 <= D <= 1024: see blp_topk_wide_supported)", who, model, D);
+    if (!wide && !blp_topk_supported(model, D, k))
         return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (64 / 128 / 256: see blp_topk_supported)", who, D);
     if (N < 0 || q_head < 0 || q_tail < 0 || ld < D || row_base < 0)
         return fail(BLP_ERR_BAD_ARG, "%s: negative size / row_base or ld < D (N=%lld q_head=%lld q_tail=%lld ld=%lld)", who,
@@ -725,24 +728,54 @@ static int topk_call(const char* who, int model, const void* table, int table_dt
         spec.row_base = filter->row_base;
     }
     if (Q == 0) return BLP_OK;
-    const size_t need = blp::topk_workspace_bytes(model, D, N, q_head, q_tail, k);
+    const size_t need = wide ? blp::topk_wide_workspace_bytes(N, q_head, q_tail, k) : blp::topk_workspace_bytes(model, D, N, q_head, q_tail, k);
     if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255u))
         return fail(BLP_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned and >= %zu bytes (got %zu)", who, need,
                     workspace_bytes);
     DeviceGuard guard(device);
     if (guard.error() != hipSuccess) return hip_fail(guard.error(), "hipSetDevice");
-    hipError_t err = blp::launch_topk(model, D, table_dtype, table, N, ld, row_base, blp::QRows::rows_of(source, fixed_row, ld_src),
-                                      blp::QRows::rows_of(rel_emb, rel_id, D), q_head, q_tail, k, spec, rows, scores, workspace,
-                                      static_cast<hipStream_t>(stream));
-    if (err != hipSuccess) return hip_fail(err, table_dtype == BLP_DTYPE_F32 ? "blp_topk launch" : "blp_topk_typed launch");
+    const blp::QRows q_fixed = blp::QRows::rows_of(source, fixed_row, ld_src), q_rel = blp::QRows::rows_of(rel_emb, rel_id, D);
+    hipError_t err;
+    if (wide)
+        err = blp::launch_topk_wide(model, D, static_cast<const float*>(table), N, ld, row_base, q_fixed, q_rel, q_head, q_tail, k, spec,
+                                    rows, scores, workspace, static_cast<hipStream_t>(stream));
+    else
+        err = blp::launch_topk(model, D, table_dtype, table, N, ld, row_base, q_fixed, q_rel, q_head, q_tail, k, spec, rows, scores,
+                               workspace, static_cast<hipStream_t>(stream));
+    if (err != hipSuccess)
+        return hip_fail(err, wide ? "blp_topk_wide launch" : table_dtype == BLP_DTYPE_F32 ? "blp_topk launch" : "blp_topk_typed launch");
     return BLP_OK;
 }
+
+// ---- filtered top-k for DistMult / ComplEx / SimplE at any width (topk_wide.hip): blp_topk's arguments, checks and codes
+int blp_topk_wide_supported(int model, int D, int k) { return valid_model(model) && blp::topk_wide_supported(model, D, k) ? 1 : 0; }
+
+size_t blp_topk_wide_workspace_bytes(int model, int64_t N, int D, int64_t q_head, int64_t q_tail, int k) {
+    if (!blp_topk_wide_supported(model, D, k) || N < 0 || q_head < 0 || q_tail < 0 || q_head + q_tail > ((1ll << 31) - 1) / k) return 0;
+    return blp::topk_wide_workspace_bytes(N, q_head, q_tail, k);
+}
+
+int blp_topk_wide(int model, const float* table, int64_t N, int D, int64_t ld, int64_t row_base, const float* source, int64_t S,
+                  int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R, const int64_t* rel_id, int64_t q_head,
+                  int64_t q_tail, int k, const blp_filter* filter, int64_t* rows, float* scores, void* workspace,
+                  size_t workspace_bytes, int device, void* stream) {
+    return topk_call("blp_topk_wide", true, model, table, BLP_DTYPE_F32, N, D, ld, row_base, source, S, ld_src, fixed_row, rel_emb, R,
+                     rel_id, q_head, q_tail, k, filter, rows, scores, workspace, workspace_bytes, device, stream);
+}
+
+#ifdef BLP_TEST_HOOKS
+size_t blp_debug_topk_wide_lds_bytes(int model, int D, int k) {
+    if (!blp_topk_wide_supported(model, D, k)) return 0;
+    const size_t head = blp::topk_wide_lds_bytes(model, blp::HEAD, D, k), tail = blp::topk_wide_lds_bytes(model, blp::TAIL, D, k);
+    return head > tail ? head : tail;
+}
+#endif
 
 int blp_topk(int model, const float* table, int64_t N, int D, int64_t ld, int64_t row_base, const float* source, int64_t S,
              int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R, const int64_t* rel_id, int64_t q_head,
              int64_t q_tail, int k, const blp_filter* filter, int64_t* rows, float* scores, void* workspace,
              size_t workspace_bytes, int device, void* stream) {
-    return topk_call("blp_topk", model, table, BLP_DTYPE_F32, N, D, ld, row_base, source, S, ld_src, fixed_row, rel_emb, R, rel_id,
+    return topk_call("blp_topk", false, model, table, BLP_DTYPE_F32, N, D, ld, row_base, source, S, ld_src, fixed_row, rel_emb, R, rel_id,
                      q_head, q_tail, k, filter, rows, scores, workspace, workspace_bytes, device, stream);
 }
 
@@ -759,7 +792,7 @@ int blp_topk_typed(int model, const void* table, int table_dtype, int64_t N, int
                    const float* source, int64_t S, int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R,
                    const int64_t* rel_id, int64_t q_head, int64_t q_tail, int k, const blp_filter* filter, int64_t* rows,
                    float* scores, void* workspace, size_t workspace_bytes, int device, void* stream) {
-    return topk_call(table_dtype == BLP_DTYPE_F32 ? "blp_topk" : "blp_topk_typed", model, table, table_dtype, N, D, ld, row_base,
+    return topk_call(table_dtype == BLP_DTYPE_F32 ? "blp_topk" : "blp_topk_typed", false, model, table, table_dtype, N, D, ld, row_base,
                      source, S, ld_src, fixed_row, rel_emb, R, rel_id, q_head, q_tail, k, filter, rows, scores, workspace,
                      workspace_bytes, device, stream);
 }

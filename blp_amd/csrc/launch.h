@@ -108,6 +108,16 @@ hipError_t launch_topk(int model, int D, int dtype, const void* table, int64_t N
 hipError_t launch_topk_merge(const int64_t* rows, const float* scores, int64_t Q, int64_t n_in, int k, int64_t* rows_out,
                              float* scores_out, hipStream_t stream);
 
+// topk_wide.hip: launch_topk for DistMult / ComplEx / SimplE at any width (D % 4 == 0, 4 <= D <= 1024; include/blp_hip.h:
+// blp_topk_wide), an f32 table; the workspace holds the partial key lists only.  topk_wide_lds_bytes: the dynamic LDS the
+// table pass of one side (HEAD / TAIL) is launched with.
+bool topk_wide_supported(int model, int D, int k);
+size_t topk_wide_workspace_bytes(int64_t N, int64_t q_head, int64_t q_tail, int k);
+size_t topk_wide_lds_bytes(int model, int side, int D, int k);
+hipError_t launch_topk_wide(int model, int D, const float* table, int64_t N, int64_t ld, int64_t row_base, const QRows q_fixed,
+                            const QRows q_rel, int64_t q_head, int64_t q_tail, int k, const FilterSpec& filter, int64_t* rows,
+                            float* scores, void* workspace, hipStream_t stream);
+
 // topk.hip's second and third stage for topk_sets.hip: the k best of (Q, n_in) keys (topk_lists.h; 0 = an empty slot) ->
 // rows / scores, and the winners of an f32 table re-scored by Scorer<>::score<true>
 hipError_t launch_topk_merge_keys(const unsigned long long* keys, int64_t Q, int64_t n_in, int k, int64_t* rows_out, float* scores_out,

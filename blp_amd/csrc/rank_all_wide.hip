@@ -10,22 +10,11 @@
 //   4. wide_bilinear_filter_finalize   64 queries per workgroup: the filter's rows re-scored by wide_pair_score,
 //                                      counts[q] = {gt, ge, gt - fgt, ge - fge}
 //
-// The table pass.  The reference sums the n terms of a score (n = D for DistMult, D / 2 for ComplEx and SimplE) in torch's
-// sum(dim=-1) order (score_direct.h: torch_inner_sum_any): 32 accumulators, accumulator a takes term 32 i + a of every
-// whole 32-term row i; for n >= 512 the accumulators are added into a second set and zeroed after rows 16 and 32; the
-// (n / 8) % 4 leftover vectors of 8 go to accumulators 0 .. 7; fold A[l] + A[8 + l] + A[16 + l] + A[24 + l]; the n % 8
-// tail terms first, then the eight folded values left to right.  That order is mapped onto EIGHT LANES PER CANDIDATE ROW:
-// lane `sub` of the eight owns accumulators 4 sub .. 4 sub + 3, so a 32-term row of a candidate is one 16-byte load per
-// lane -- the eight lanes read one 128-B line -- and the leftover vectors belong to lanes 0 and 1.  A wave is 8 candidate
-// groups; each group holds kAwRows candidate rows against the kAwQueries queries of the workgroup's chunk, i.e.
-// kAwRows x kAwQueries x 4 accumulators per lane (twice that for n >= 512: CASCADE), all in registers.  The queries'
-// coefficients -- what Scorer<MODEL, SIDE, D>::coef hoists (score_core.h), computed by the workgroup when it takes the
-// chunk -- sit in LDS as K arrays of n floats per query; a lane reads the 16 bytes of its four columns, the eight groups
-// the same addresses (broadcast).  The fold is three v_add with a DPP row shift (lanes 0 and 1 get accumulators 0 .. 7
-// folded), the last eight additions take the values by DPP quad broadcasts from lanes 0 and 1; lane 0 of a group
-// compares with the true key and the wave counts by ballot into scalar counters, flushed once per (chunk, slab) with a
-// 64-bit atomic (gt low word, ge high word).  Additions of all-zero upper cascade levels are dropped: they can turn -0
-// into +0 only, which no > / >= sees.
+// The table pass.  wide_bilinear.h holds its arithmetic (shared with topk_wide.hip): the reference's sum order mapped onto
+// eight lanes per candidate row, kAwRows rows of a group against the kAwQueries queries of the workgroup's chunk, the
+// coefficients in LDS (wide_stage_coef), the scores of a trip in registers (wide_trip).  Here lane 0 of a group compares
+// with the true key and the wave counts by ballot into scalar counters, flushed once per (chunk, slab) with a 64-bit atomic
+// (gt low word, ge high word).
 //
 // Grid: x = query chunks (at most kAwMaxGridX, the workgroup strides), y = candidate slabs of about kAwSlabBytes (one
 // slab stays in an XCD's L2 while the chunks that run together stream it), fewer rows per slab when there are few chunks.
@@ -35,6 +24,7 @@
 #include "launch.h"
 #include "rank_common.h"
 #include "score_core.h"
+#include "wide_bilinear.h"
 
 #pragma clang fp contract(off)
 
@@ -42,173 +32,16 @@ namespace blp {
 
 namespace {
 
-constexpr int kAwQueries = 8;                          // queries of a chunk
-constexpr int kAwRows = 2;                             // candidate rows of an eight-lane group
-constexpr int kAwWaves = 4;
-constexpr int kAwBlockRows = kAwWaves * 8 * kAwRows;   // rows a workgroup takes per trip
-constexpr int kAwMaxD = 1024;
 constexpr int64_t kAwSlabBytes = 2 << 20;
 constexpr int64_t kAwMaxGridX = 32768, kAwMaxGridY = 32768;
-
-// One summand of the score with the candidate's elements ea = e[j] and (two-halves models) eb = e[H + j], and the query's K
-// coefficients at j: the operations of Scorer<MODEL, SIDE, D>::score / coef (score_core.h), i.e. of score_direct<MODEL>.
-template <int MODEL, int SIDE>
-struct WideTerm;
-
-template <>
-struct WideTerm<DISTMULT, TAIL> {  // (h * r) * e
-    static constexpr int K = 1;
-    static constexpr bool kHalves = false;
-    __device__ __forceinline__ static float coef(const float* f, const float* r, int j, int H, int k) { return f[j] * r[j]; }
-    __device__ __forceinline__ static float term(float ea, float eb, const float (&c)[K]) { return c[0] * ea; }
-};
-template <>
-struct WideTerm<DISTMULT, HEAD> {  // (e * r) * t
-    static constexpr int K = 2;
-    static constexpr bool kHalves = false;
-    __device__ __forceinline__ static float coef(const float* f, const float* r, int j, int H, int k) { return k == 0 ? r[j] : f[j]; }
-    __device__ __forceinline__ static float term(float ea, float eb, const float (&c)[K]) {
-        const float x = ea * c[0];
-        return x * c[1];
-    }
-};
-template <>
-struct WideTerm<COMPLEX, TAIL> {  // f = head: the four r * h products are hoisted
-    static constexpr int K = 4;
-    static constexpr bool kHalves = true;
-    __device__ __forceinline__ static float coef(const float* f, const float* r, int j, int H, int k) {
-        switch (k) {
-        case 0: return r[j] * f[j];
-        case 1: return r[j] * f[H + j];
-        case 2: return r[H + j] * f[j];
-        default: return r[H + j] * f[H + j];
-        }
-    }
-    __device__ __forceinline__ static float term(float ea, float eb, const float (&c)[K]) {
-        const float a = c[0] * ea;
-        const float b = c[1] * eb;
-        const float cc = c[2] * eb;
-        const float d = c[3] * ea;
-        float s = a + b;
-        s = s + cc;
-        return s - d;
-    }
-};
-template <>
-struct WideTerm<COMPLEX, HEAD> {  // f = tail: rr, ri, tr, ti as they are
-    static constexpr int K = 4;
-    static constexpr bool kHalves = true;
-    __device__ __forceinline__ static float coef(const float* f, const float* r, int j, int H, int k) {
-        switch (k) {
-        case 0: return r[j];
-        case 1: return r[H + j];
-        case 2: return f[j];
-        default: return f[H + j];
-        }
-    }
-    __device__ __forceinline__ static float term(float ea, float eb, const float (&c)[K]) {
-        float a = c[0] * ea;   a = a * c[2];    // (rr*hr)*tr
-        float b = c[0] * eb;   b = b * c[3];    // (rr*hi)*ti
-        float cc = c[1] * ea;  cc = cc * c[3];  // (ri*hr)*ti
-        float d = c[1] * eb;   d = d * c[2];    // (ri*hi)*tr
-        float s = a + b;
-        s = s + cc;
-        return s - d;
-    }
-};
-template <>
-struct WideTerm<SIMPLE, TAIL> {  // f = head = [hh | ht], e = tail = [th | tt]: (hh*ra)*tt + (th*rb)*ht
-    static constexpr int K = 3;
-    static constexpr bool kHalves = true;
-    __device__ __forceinline__ static float coef(const float* f, const float* r, int j, int H, int k) {
-        return k == 0 ? f[j] * r[j] : (k == 1 ? r[H + j] : f[H + j]);
-    }
-    __device__ __forceinline__ static float term(float ea, float eb, const float (&c)[K]) {
-        const float a = c[0] * eb;
-        float b = ea * c[1];
-        b = b * c[2];
-        return a + b;
-    }
-};
-template <>
-struct WideTerm<SIMPLE, HEAD> {  // f = tail = [th | tt], e = head = [hh | ht]
-    static constexpr int K = 3;
-    static constexpr bool kHalves = true;
-    __device__ __forceinline__ static float coef(const float* f, const float* r, int j, int H, int k) {
-        return k == 0 ? r[j] : (k == 1 ? f[H + j] : f[j] * r[H + j]);
-    }
-    __device__ __forceinline__ static float term(float ea, float eb, const float (&c)[K]) {
-        float a = ea * c[0];
-        a = a * c[1];
-        const float b = c[2] * eb;
-        return a + b;
-    }
-};
-
-template <int S>
-__device__ __forceinline__ float row_shl(float x) {  // lane l <- lane l + S of its row of 16
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x100 + S, 0xf, 0xf, true));
-}
-
-// four columns of kAwRows candidate rows
-template <bool HALVES>
-struct WideCols {
-    float a[kAwRows][4];
-    float b[HALVES ? kAwRows : 1][4];
-};
-
-template <bool HALVES>
-__device__ __forceinline__ void wide_load(WideCols<HALVES>& e, const float* const (&ptr)[kAwRows], int col, int H) {
-#pragma unroll
-    for (int r = 0; r < kAwRows; ++r) {
-        const float4 v = *reinterpret_cast<const float4*>(ptr[r] + col);
-        e.a[r][0] = v.x; e.a[r][1] = v.y; e.a[r][2] = v.z; e.a[r][3] = v.w;
-        if constexpr (HALVES) {  // H is even, not always a multiple of 4: two 8-byte loads
-            const float2 lo = *reinterpret_cast<const float2*>(ptr[r] + H + col);
-            const float2 hi = *reinterpret_cast<const float2*>(ptr[r] + H + col + 2);
-            e.b[r][0] = lo.x; e.b[r][1] = lo.y; e.b[r][2] = hi.x; e.b[r][3] = hi.y;
-        } else {
-            e.b[0][0] = e.b[0][1] = e.b[0][2] = e.b[0][3] = 0.0f;  // never used
-        }
-    }
-}
-
-// acc[q][r][c] += term of column col + c (col: the lane's first of four) for every query of the chunk
-template <int MODEL, int SIDE>
-__device__ __forceinline__ void wide_step(float (&acc)[kAwQueries][kAwRows][4], const WideCols<WideTerm<MODEL, SIDE>::kHalves>& e,
-                                          const float* coef, int n4, int col) {
-    using T = WideTerm<MODEL, SIDE>;
-#pragma unroll
-    for (int q = 0; q < kAwQueries; ++q) {
-        float c4[T::K][4];
-#pragma unroll
-        for (int k = 0; k < T::K; ++k) {
-            const float4 v = *reinterpret_cast<const float4*>(coef + (q * T::K + k) * n4 + col);
-            c4[k][0] = v.x; c4[k][1] = v.y; c4[k][2] = v.z; c4[k][3] = v.w;
-        }
-#pragma unroll
-        for (int r = 0; r < kAwRows; ++r) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                float ck[T::K];
-#pragma unroll
-                for (int k = 0; k < T::K; ++k) ck[k] = c4[k][c];
-                acc[q][r][c] = acc[q][r][c] + T::term(e.a[r][c], e.b[T::kHalves ? r : 0][c], ck);
-            }
-        }
-    }
-}
 
 template <int MODEL, int SIDE, bool CASCADE>
 __global__ __launch_bounds__(kAwWaves * 64) void rank_all_wide_kernel(const float* __restrict__ table, int64_t N, int64_t ld, int D,
                                                                       const QRows q_fixed, const QRows q_rel,
                                                                       const float* __restrict__ key_true, int64_t q_off, int64_t nq,
                                                                       int64_t slab_rows, unsigned long long* __restrict__ acc_out) {
-    using T = WideTerm<MODEL, SIDE>;
-    constexpr int K = T::K, QC = kAwQueries, R = kAwRows;
+    constexpr int QC = kAwQueries, R = kAwRows;
     extern __shared__ __attribute__((aligned(16))) float aw_coef[];  // [query of the chunk][K][n4]
-    const int H = D / 2, n = MODEL == DISTMULT ? D : H, n4 = (n + 3) & ~3;
-    const int size_ilp = n / 32, vec_size = n / 8, n_left = vec_size - 4 * size_ilp;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = lane >> 3, sub = lane & 7;
     const int64_t row_lo = (int64_t)blockIdx.y * slab_rows, row_hi = row_lo + slab_rows < N ? row_lo + slab_rows : N;
     const int64_t n_chunks = (nq + QC - 1) / QC;
@@ -216,12 +49,7 @@ __global__ __launch_bounds__(kAwWaves * 64) void rank_all_wide_kernel(const floa
         const int64_t q0 = q_off + chunk * QC;
         const int live_q = (int)(q_off + nq - q0 < QC ? q_off + nq - q0 : QC);
         __syncthreads();  // the previous chunk's coefficients have been read
-        for (int x = threadIdx.x; x < QC * K * n4; x += kAwWaves * 64) {
-            const int q = x / (K * n4), rem = x - q * (K * n4), k = rem / n4, j = rem - k * n4;
-            float v = 0.0f;
-            if (q < live_q && j < n) v = T::coef(q_fixed.row(q0 + q), q_rel.row(q0 + q), j, H, k);
-            aw_coef[x] = v;
-        }
+        wide_stage_coef<MODEL, SIDE>(aw_coef, q_fixed, q_rel, q0, live_q, D);
         __syncthreads();
         float kt[QC];
 #pragma unroll
@@ -232,110 +60,23 @@ __global__ __launch_bounds__(kAwWaves * 64) void rank_all_wide_kernel(const floa
 
         for (int64_t rb = row_lo + wave * (8 * R); rb < row_hi; rb += kAwBlockRows) {  // wave-uniform
             const float* base[R];  // the group's rows (past the slab: its last row, not counted)
-            const float* ptr[R];   // ... at the lane's four columns
             bool live[R];
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const int64_t row = rb + grp + 8 * r;
                 live[r] = row < row_hi;
                 base[r] = table + (live[r] ? row : row_hi - 1) * ld;
-                ptr[r] = base[r] + 4 * sub;
             }
-            float acc[QC][R][4];
-            float up[CASCADE ? QC : 1][R][4];
-#pragma unroll
-            for (int q = 0; q < QC; ++q)
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        acc[q][r][c] = 0.0f;
-                        if (CASCADE) up[CASCADE ? q : 0][r][c] = 0.0f;
-                    }
-            // whole rows of 32 terms, the next row's loads in flight behind the current row's arithmetic
-            WideCols<T::kHalves> cur;
-            if (size_ilp > 0) wide_load<T::kHalves>(cur, ptr, 0, H);
-#pragma unroll 1
-            for (int i = 0; i < size_ilp; ++i) {
-                WideCols<T::kHalves> nxt;
-                wide_load<T::kHalves>(nxt, ptr, i + 1 < size_ilp ? 32 * (i + 1) : 32 * i, H);
-                wide_step<MODEL, SIDE>(acc, cur, aw_coef, n4, 32 * i + 4 * sub);
-                cur = nxt;
-                if constexpr (CASCADE) {
-                    if (((i + 1) & 15) == 0) {  // after rows 16 and 32: one level up
-#pragma unroll
-                        for (int q = 0; q < QC; ++q)
-#pragma unroll
-                            for (int r = 0; r < R; ++r)
-#pragma unroll
-                                for (int c = 0; c < 4; ++c) {
-                                    up[CASCADE ? q : 0][r][c] = up[CASCADE ? q : 0][r][c] + acc[q][r][c];
-                                    acc[q][r][c] = 0.0f;
-                                }
-                    }
-                }
-            }
-            if constexpr (CASCADE) {
-#pragma unroll
-                for (int q = 0; q < QC; ++q)
-#pragma unroll
-                    for (int r = 0; r < R; ++r)
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) acc[q][r][c] = acc[q][r][c] + up[CASCADE ? q : 0][r][c];
-            }
-            // the leftover vectors of 8: accumulators 0 .. 7, i.e. lanes 0 and 1 of the group
-            for (int v = 0; v < n_left; ++v) {
-                if (sub < 2) {
-                    const int col = 32 * size_ilp + 8 * v;
-                    WideCols<T::kHalves> e;
-                    wide_load<T::kHalves>(e, ptr, col, H);
-                    wide_step<MODEL, SIDE>(acc, e, aw_coef, n4, col + 4 * sub);
-                }
-            }
-            // the n % 8 tail terms, one after the other (every lane of the group the same)
-            float tail[QC][R];
-#pragma unroll
-            for (int q = 0; q < QC; ++q)
-#pragma unroll
-                for (int r = 0; r < R; ++r) tail[q][r] = 0.0f;
-            for (int j = 8 * vec_size; j < n; ++j) {
-                float ea[R], eb[R];
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    ea[r] = base[r][j];
-                    eb[r] = T::kHalves ? base[r][H + j] : 0.0f;
-                }
-#pragma unroll
-                for (int q = 0; q < QC; ++q) {
-                    float ck[K];
-#pragma unroll
-                    for (int k = 0; k < K; ++k) ck[k] = aw_coef[(q * K + k) * n4 + j];
-#pragma unroll
-                    for (int r = 0; r < R; ++r) tail[q][r] = tail[q][r] + T::term(ea[r], eb[r], ck);
-                }
-            }
-            // fold, the last eight additions, the comparison
+            float s[QC][R];
+            wide_trip<MODEL, SIDE, CASCADE>(s, base, aw_coef, D, sub);
+            // lane 0 of a group compares with the true key; the wave counts by ballot
 #pragma unroll
             for (int q = 0; q < QC; ++q) {
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
-                    float V[4];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {  // lanes 0, 1: A[l] + A[8 + l] + A[16 + l] + A[24 + l], l = 4 sub + c
-                        const float a = acc[q][r][c];
-                        float v = a + row_shl<2>(a);
-                        v = v + row_shl<4>(a);
-                        V[c] = v + row_shl<6>(a);
-                    }
-                    float s = tail[q][r];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) s = s + quad_bcast<0>(V[c]);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) s = s + quad_bcast<1>(V[c]);
-                    const float key = MODEL == SIMPLE ? s / 2.0f : s;
                     const bool mine = live[r] && sub == 0;
-                    cgt[q] += (unsigned)__popcll(__ballot(mine && key > kt[q]));
-                    cge[q] += (unsigned)__popcll(__ballot(mine && key >= kt[q]));
+                    cgt[q] += (unsigned)__popcll(__ballot(mine && s[q][r] > kt[q]));
+                    cge[q] += (unsigned)__popcll(__ballot(mine && s[q][r] >= kt[q]));
                 }
             }
         }
@@ -346,61 +87,6 @@ __global__ __launch_bounds__(kAwWaves * 64) void rank_all_wide_kernel(const floa
                     atomicAdd(acc_out + q0 + q, (unsigned long long)cgt[q] | ((unsigned long long)cge[q] << 32));
         }
     }
-}
-
-// One (candidate, query) pair by eight lanes, straight from the three vectors: the table pass's mapping and operations (lane
-// `sub` owns accumulators 4 sub .. 4 sub + 3, the same fold and last additions), the coefficients computed in place by the
-// expressions the pass stages in LDS -- so a pair gets the number the pass gives it, bit for bit.  Every lane of the wave must
-// call (the fold reads neighbouring lanes); the result is valid in lanes 0 .. 3 of the eight.
-template <int MODEL, int SIDE>
-__device__ __forceinline__ float wide_pair_score(const float* __restrict__ e, const float* __restrict__ f, const float* __restrict__ r,
-                                                 int D, int sub) {
-    using T = WideTerm<MODEL, SIDE>;
-    constexpr int K = T::K;
-    const int H = D / 2, n = MODEL == DISTMULT ? D : H;
-    const int size_ilp = n / 32, vec_size = n / 8, n_left = vec_size - 4 * size_ilp;
-    auto term_at = [&](int j) {
-        float ck[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) ck[k] = T::coef(f, r, j, H, k);
-        return T::term(e[j], T::kHalves ? e[H + j] : 0.0f, ck);
-    };
-    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f}, up[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    for (int i = 0; i < size_ilp; ++i) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[c] = acc[c] + term_at(32 * i + 4 * sub + c);
-        if (((i + 1) & 15) == 0) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                up[c] = up[c] + acc[c];
-                acc[c] = 0.0f;
-            }
-        }
-    }
-    if (n >= 512) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[c] = acc[c] + up[c];
-    }
-    for (int v = 0; v < n_left; ++v) {
-        if (sub < 2) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc[c] = acc[c] + term_at(32 * size_ilp + 8 * v + 4 * sub + c);
-        }
-    }
-    float s = 0.0f;
-    for (int j = 8 * vec_size; j < n; ++j) s = s + term_at(j);
-    float V[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        float v = acc[c] + row_shl<2>(acc[c]);
-        v = v + row_shl<4>(acc[c]);
-        V[c] = v + row_shl<6>(acc[c]);
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) s = s + quad_bcast<0>(V[c]);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) s = s + quad_bcast<1>(V[c]);
-    return MODEL == SIMPLE ? s / 2.0f : s;
 }
 
 // True-entity keys, eight lanes per query (wide_pair_score); the queries' accumulators start at zero.

@@ -36,24 +36,6 @@ __host__ __device__ inline int64_t topk_sets_slabs_of(int64_t n, int s_max) {
     return s < 1 ? 1 : (s > s_max ? s_max : s);
 }
 
-// unfiltered() (topk.hip) for a gathered tile: the lanes of `mask` whose candidate -- lane b holds table row lrow of ITS OWN,
-// not row0 + b -- query q's filter segment does NOT remove.  The segment is read 64 entries at a time (filter_row: exclude,
-// ent2idx, row_base as filter_finalize applies them); every admitted lane's row is broadcast with one shuffle and looked up
-// with one compare + ballot per chunk of the segment.
-__device__ __forceinline__ u64 unfiltered_rows(const FilterSpec& f, int64_t q, int64_t N, int lrow, u64 mask, int lane) {
-    const int64_t lo = f.lo[q], hi = f.hi[q];
-    for (int64_t c = lo; c < hi && mask; c += 64) {
-        const int64_t v = c + lane < hi ? filter_row(f, q, c + lane, N) : -1;
-        u64 m = mask;
-        while (m) {
-            const int b = __builtin_ctzll(m);
-            m &= m - 1;
-            if (__ballot(v == (int64_t)__shfl(lrow, b))) mask &= ~(1ull << b);
-        }
-    }
-    return mask;
-}
-
 // nq queries of one side, q0 .. (the call's numbering), against the wave's gathered tile; coef = the coefficient row of q0
 template <int MODEL, int SIDE, int D>
 __device__ __forceinline__ void topk_sets_side(const float (&e)[D], bool valid, int lrow, int64_t row_base, int64_t N,

@@ -401,6 +401,33 @@ def topk(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, filte
     ``table`` may be float16 / bfloat16 (blp_topk_typed: the result is the float32 table's, widened exactly, read at half the
     bytes); ``source`` and ``rel_emb`` are float32.
     Returns (rows (Q, k) int64, scores (Q, k) float32); ``out`` may give both."""
+    return _topk(False, rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, filter, row_base, out)
+
+
+def topk_wide_supported(rel_model, dim, k, dtype=torch.float32):
+    """True if topk_wide takes this model, width, k and table dtype (blp_topk_wide_supported: distmult / complex / simple,
+    D % 4 == 0, 4 <= D <= 1024 -- the BOW / DKRL encoders' 300 and 768 --, 1 <= k <= 256; a float32 table only)."""
+    if dtype != torch.float32:
+        return False
+    return bool(_lib.lib().blp_topk_wide_supported(_lib.MODEL_IDS[rel_model], int(dim), int(k)))
+
+
+def topk_wide_workspace_bytes(rel_model, N, D, q_head, q_tail, k):
+    """Bytes of topk_wide's workspace: the partial key lists only -- never a function of D, constant in N from 2^17 rows on
+    (0: not supported, a negative size, or Q x k >= 2^31)."""
+    return int(_lib.lib().blp_topk_wide_workspace_bytes(_lib.MODEL_IDS[rel_model], int(N), int(D), int(q_head), int(q_tail), int(k)))
+
+
+def topk_wide(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, filter=None, row_base=0, out=None):
+    """topk for DistMult / ComplEx / SimplE at any width D % 4 == 0, 4 <= D <= 1024 on a float32 table (blp_topk_wide: eight
+    lanes per candidate row sum in the reference's order, the winners' scores come straight from the selection keys): same
+    arguments, same rows and scores -- score_fn's bit for bit."""
+    return _topk(True, rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, filter, row_base, out)
+
+
+def _topk(wide, rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, filter, row_base, out):
+    """topk (blp_topk_typed) and topk_wide (blp_topk_wide): one argument handling, two entries."""
+    who = "topk_wide" if wide else "topk"
     _require_device(table, source, fixed_row, rel_emb, rel_ids)
     if source is table and table.dtype != torch.float32:
         raise TypeError("a 16-bit table needs a float32 `source` for the queries' vectors (ops.gather_triple_vectors + build_queries(by_position=True))")
@@ -418,10 +445,13 @@ def topk(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, filte
         raise ValueError("fixed_row and rel_ids need one entry per query; rel_emb must be (R, D)")
     if not 0 <= q_head <= Q:
         raise ValueError(f"q_head = {q_head} outside [0, {Q}]")
-    if not topk_supported(rel_model, D, k, table.dtype):
+    if wide and not topk_wide_supported(rel_model, D, k, table.dtype):
+        raise ValueError(f"topk_wide: {rel_model} at D = {D}, k = {k} not supported (distmult / complex / simple, D % 4 == 0, "
+                         "4 <= D <= 1024, 1 <= k <= 256, a float32 table): see topk_wide_supported")
+    if not wide and not topk_supported(rel_model, D, k, table.dtype):
         raise ValueError(f"topk: D = {D}, k = {k} not supported (D in 64 / 128 / 256, 1 <= k <= 256): see topk_supported")
     if filter is not None and int(filter.row_base) != int(row_base):
-        raise ValueError(f"topk: the filter's row_base {filter.row_base} differs from row_base {row_base}")
+        raise ValueError(f"{who}: the filter's row_base {filter.row_base} differs from row_base {row_base}")
     dev = table.device
     if out is None:
         out = (torch.empty((Q, k), dtype=torch.int64, device=dev), torch.empty((Q, k), dtype=torch.float32, device=dev))
@@ -434,16 +464,21 @@ def topk(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, filte
     L = _lib.lib()
     model = _lib.MODEL_IDS[rel_model]
     tdt = TABLE_DTYPES[table.dtype]
-    ws_bytes = L.blp_topk_typed_workspace_bytes(model, tdt, N, D, q_head, Q - q_head, k)
+    if wide:  # (a float32 table: blp_topk's argument list, without the storage type)
+        ws_bytes = L.blp_topk_wide_workspace_bytes(model, N, D, q_head, Q - q_head, k)
+        entry, dtype_arg = L.blp_topk_wide, ()
+    else:
+        ws_bytes = L.blp_topk_typed_workspace_bytes(model, tdt, N, D, q_head, Q - q_head, k)
+        entry, dtype_arg = L.blp_topk_typed, (tdt,)
     stream = torch._C._cuda_getCurrentRawStream(dev.index)
     workspace = _workspace(dev, stream, ws_bytes)
     spec = None if filter is None else _filter_spec(filter, Q, dev)
-    status = L.blp_topk_typed(model, table.data_ptr(), tdt, N, D, table.stride(0) if tdt or N > 1 else D, int(row_base),
-                              source.data_ptr(), source.shape[0], source.stride(0) if source.shape[0] > 1 else D, fixed_row.data_ptr(),
-                              rel_emb.data_ptr(), rel_emb.shape[0], rel_ids.data_ptr(), q_head, Q - q_head, k, spec, rows.data_ptr(),
-                              scores.data_ptr(), workspace.data_ptr(), ws_bytes, dev.index, stream)
+    status = entry(model, table.data_ptr(), *dtype_arg, N, D, table.stride(0) if tdt or N > 1 else D, int(row_base),
+                   source.data_ptr(), source.shape[0], source.stride(0) if source.shape[0] > 1 else D, fixed_row.data_ptr(),
+                   rel_emb.data_ptr(), rel_emb.shape[0], rel_ids.data_ptr(), q_head, Q - q_head, k, spec, rows.data_ptr(),
+                   scores.data_ptr(), workspace.data_ptr(), ws_bytes, dev.index, stream)
     if status:
-        _lib.check(status, "blp_topk_typed" if tdt else "blp_topk")
+        _lib.check(status, "blp_topk_wide" if wide else "blp_topk_typed" if tdt else "blp_topk")
     return rows, scores
 
 

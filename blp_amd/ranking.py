@@ -548,6 +548,17 @@ def _topk_dense(score_fn, table, fixed, rel, q_head, k, row_base, filt, max_matr
     return rows_out, scores_out
 
 
+def _topk_one_set(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, filter=None, row_base=0):
+    """ops.topk's call served by ops.topk_sets_wide (TransE at the widths blp_topk is not compiled for): ONE candidate set
+    that is the local table, every query in its group -- the same contract, the same bits."""
+    dev, N, Q = table.device, table.shape[0], fixed_row.shape[0]
+    # the three two-entry offset arrays in ONE host-to-device copy; the set's rows are made on the device
+    ptr = torch.tensor([0, N, 0, q_head, 0, Q - q_head], dtype=torch.int64, device=dev)
+    return ops.topk_sets_wide(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, k, ptr[0:2],
+                              torch.arange(row_base, row_base + N, dtype=torch.int64, device=dev), ptr[2:4], ptr[4:6],
+                              filter=filter, row_base=row_base)
+
+
 def predict_links(model, table, triples, k, ent2idx, *, side="both", filter_index=None, entities=None, group=None, world=1,
                   rank=0, num_entities=None):
     """Answer link-prediction queries: for every triple (head, tail, rel) of ``triples`` (T, 3) the k table rows the model
@@ -561,9 +572,13 @@ def predict_links(model, table, triples, k, ent2idx, *, side="both", filter_inde
     entities     optional (num_entities,) entity id of every table row: ids instead of rows are returned
     Returns (rows or ids (Q, k) int64, scores (Q, k) float32): descending score, ties by ascending row, NaN last; -1 / NaN
     beyond the candidates left.  Scores are score_fn's values bit for bit.  HIP tensors at a width blp_topk takes: blp_topk
-    (one call per rank; shards merged by one all-gather of the (Q, k) lists + blp_topk_merge); otherwise the reference's
-    dense route (score_fn + a stable sort) in query chunks.  A float16 / bfloat16 HIP table takes blp_topk_typed, which reads
-    the 16-bit rows as they are: rows and scores are those of the same table widened to float32, bit for bit."""
+    (one call per rank; shards merged by one all-gather of the (Q, k) lists + blp_topk_merge).  A float16 / bfloat16 HIP
+    table takes blp_topk_typed, which reads the 16-bit rows as they are: rows and scores are those of the same table widened
+    to float32, bit for bit.  HIP tensors at the other widths D % 4 == 0, 4 <= D <= 1024 (the BOW / DKRL encoders' 300 and
+    768), k <= 256: DistMult / ComplEx / SimplE on a float32 table take blp_topk_wide; TransE (float32, float16 or bfloat16
+    table) takes blp_topk_sets_wide with ONE candidate set that is the local table -- the same contract, the same bits, the
+    same merge of shards.  Everything else (CPU tensors, k > 256, other widths, the bilinear models on a 16-bit table at
+    those widths) takes the reference's dense route (score_fn + a stable sort) in query chunks."""
     model = _module(model)
     if side not in ("head", "tail", "both"):
         raise ValueError(f"side must be 'head', 'tail' or 'both', got {side!r}")
@@ -598,7 +613,17 @@ def predict_links(model, table, triples, k, ent2idx, *, side="both", filter_inde
         source, src_rows = fixed_vecs, torch.arange(Q, device=device)
     else:
         source, src_rows = table, fixed_rows
-    fused = table.is_cuda and ops.topk_supported(model.rel_model, D, k, table.dtype)
+    # the fused call this table takes, if any: blp_topk at its widths; at the others blp_topk_wide (the bilinear models, a
+    # float32 table) or blp_topk_sets_wide with the local table as the one candidate set (TransE)
+    route = None
+    if table.is_cuda:
+        if ops.topk_supported(model.rel_model, D, k, table.dtype):
+            route = ops.topk
+        elif ops.topk_wide_supported(model.rel_model, D, k, table.dtype):
+            route = ops.topk_wide
+        elif ops.topk_sets_wide_supported(model.rel_model, D, k, table.dtype):
+            route = _topk_one_set
+    fused = route is not None
     if fused and table.dtype != torch.float32:
         # the kernels take float32 query vectors: the Q fixed rows, widened (exact; after the sum on several ranks -- x + 0
         # is exact in 16 bits too)
@@ -610,7 +635,7 @@ def predict_links(model, table, triples, k, ent2idx, *, side="both", filter_inde
         filt = ops.SegmentFilter(seg.seg_lo[sel].contiguous(), seg.seg_hi[sel].contiguous(), seg.values,
                                  seg.exclude[sel].contiguous(), seg.ent2idx, row_lo)
     if fused:
-        rows, scores = ops.topk(model.rel_model, table, source, src_rows, rel_w, rel_ids, q_head, k, filter=filt, row_base=row_lo)
+        rows, scores = route(model.rel_model, table, source, src_rows, rel_w, rel_ids, q_head, k, filter=filt, row_base=row_lo)
     else:
         dense_filt = None if filt is None else (filt.seg_lo, filt.seg_hi, filt.values, filt.exclude, filt.ent2idx)
         rows, scores = _topk_dense(model.score_fn, table, source[src_rows], rel_w[rel_ids], q_head, k, row_lo, dense_filt)

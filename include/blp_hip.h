@@ -527,6 +527,26 @@ int blp_topk_typed(int model, const void *table, int table_dtype, int64_t N, int
                    const float *source, int64_t S, int64_t ld_src, const int64_t *fixed_row, const float *rel_emb, int64_t R,
                    const int64_t *rel_id, int64_t q_head, int64_t q_tail, int k, const blp_filter *filter, int64_t *rows,
                    float *scores, void *workspace, size_t workspace_bytes, int device, void *stream);
+/* blp_topk for DistMult / ComplEx / SimplE at ANY width D % 4 == 0, 4 <= D <= 1024 (the bag-of-words / DKRL encoders' 300 and
+ * 768), 1 <= k <= 256, an f32 table (blp_topk_wide_supported; 0 for TransE -- blp_topk_sets_wide with one set serves it -- and
+ * for anything else).  The contract is blp_topk's word for word: the same arguments in the same order, the queries as rows of
+ * source / rel_emb, global rows [row_base, row_base + N), the same order of the k slots, filtered rows removed, -1 / NaN
+ * slots, score_fn's values bit for bit (sign of zero included), the same limits, alignment rules, checks and status codes
+ * (BLP_ERR_UNSUPPORTED_DIM where blp_topk_wide_supported says 0), deterministic whatever the grid, asynchronous on `stream`,
+ * no allocation, no host synchronisation.  At D in {64, 128, 256} it is a second implementation of blp_topk's bits.
+ * One code object for every width: eight lanes per candidate row sum in the reference's order from registers, the queries'
+ * coefficients live in LDS, and the winners' scores come straight from the selection keys (at most three launches).
+ * Workspace: blp_topk_wide_workspace_bytes(...) bytes, 256-B aligned: only the partial lists, exactly
+ *   round_up_256(8 k Q S),  S = max(1, min(2048 / (ceil(q_head / 8) + ceil(q_tail / 8)), ceil(N / 64)))  (integer division)
+ * -- independent of D, constant in N from N = 2^17 rows on, at most 8 k (Q + 16 384) + 256 bytes; 0 where unsupported, for a
+ * negative size and where Q x k >= 2^31.
+ * (Added after 6.0.0 without a version change: no existing entry point changed.) */
+int blp_topk_wide_supported(int model, int D, int k);
+size_t blp_topk_wide_workspace_bytes(int model, int64_t N, int D, int64_t q_head, int64_t q_tail, int k);
+int blp_topk_wide(int model, const float *table, int64_t N, int D, int64_t ld, int64_t row_base, const float *source, int64_t S,
+                  int64_t ld_src, const int64_t *fixed_row, const float *rel_emb, int64_t R, const int64_t *rel_id, int64_t q_head,
+                  int64_t q_tail, int k, const blp_filter *filter, int64_t *rows, float *scores, void *workspace,
+                  size_t workspace_bytes, int device, void *stream);
 
 /* --------------------------------------------------------------------------------------------
  * Per-query candidate lists: RANK and SCORE a query (h, r, ?) / (?, r, t) against a list of table rows that belongs to that
@@ -921,6 +941,10 @@ int blp_debug_gemm_dump(float *scores, float *eps);
 /* Forget `device`'s self-test verdict: the next blp_selftest / bilinear block tests again (with knob "mfma_selftest" = 1 it
  * then reports a violation whatever it measures -- how tests reach the f32-chain route). */
 int blp_debug_reset_selftest(int device);
+
+/* The dynamic LDS bytes blp_topk_wide's table pass is launched with at (model, D, k): the larger of its two sides; 0 where
+ * blp_topk_wide_supported says 0.  Host arithmetic only (the launch code's own function). */
+size_t blp_debug_topk_wide_lds_bytes(int model, int D, int k);
 #endif
 
 #ifdef __cplusplus
