@@ -34,6 +34,7 @@ SYMBOLS = ("blp_version", "blp_last_error", "blp_device_caps", "blp_selftest", "
            "blp_rank_sets_supported", "blp_rank_sets_workspace_bytes", "blp_rank_sets",
            "blp_rank_sets_typed_supported", "blp_rank_sets_typed_workspace_bytes", "blp_rank_sets_typed",
            "blp_rank_sets_wide_supported", "blp_rank_sets_wide_workspace_bytes", "blp_rank_sets_wide",
+           "blp_rank_sets_wide_bilinear_supported", "blp_rank_sets_wide_bilinear_workspace_bytes", "blp_rank_sets_wide_bilinear",
            "blp_topk_sets_supported", "blp_topk_sets_workspace_bytes", "blp_topk_sets",
            "blp_topk_sets_typed_supported", "blp_topk_sets_typed_workspace_bytes", "blp_topk_sets_typed",
            "blp_topk_sets_wide_supported", "blp_topk_sets_wide_workspace_bytes", "blp_topk_sets_wide",
@@ -254,7 +255,10 @@ def _load(path, hooks):
                                       _i64, _i64, _vp, _vp, ctypes.POINTER(BlpFilter), _vp, _vp, _sz, _i, _vp]
     for wide, typed in ((L.blp_rank_sets_wide_supported, L.blp_rank_sets_typed_supported),
                         (L.blp_rank_sets_wide_workspace_bytes, L.blp_rank_sets_typed_workspace_bytes),
-                        (L.blp_rank_sets_wide, L.blp_rank_sets_typed)):  # blp_rank_sets_typed's signatures, by design
+                        (L.blp_rank_sets_wide, L.blp_rank_sets_typed),
+                        (L.blp_rank_sets_wide_bilinear_supported, L.blp_rank_sets_typed_supported),
+                        (L.blp_rank_sets_wide_bilinear_workspace_bytes, L.blp_rank_sets_typed_workspace_bytes),
+                        (L.blp_rank_sets_wide_bilinear, L.blp_rank_sets_typed)):  # blp_rank_sets_typed's signatures, by design
         wide.restype, wide.argtypes = typed.restype, list(typed.argtypes)
     L.blp_topk_sets_supported.restype = _i
     L.blp_topk_sets_supported.argtypes = [_i, _i, _i]

@@ -1105,9 +1105,11 @@ size_t blp_rank_sets_workspace_bytes(int model, int D, int64_t q_head, int64_t q
     return blp::rank_sets_workspace_bytes(D, q_head, q_tail, G);
 }
 
-// blp_rank_sets, blp_rank_sets_typed and blp_rank_sets_wide: the argument checks (messages under the entry's name `who`), then
-// the launch (wide: rank_sets_wide.hip)
-static int rank_sets_call(const char* who, bool wide, int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld,
+// blp_rank_sets, blp_rank_sets_typed, blp_rank_sets_wide and blp_rank_sets_wide_bilinear: the argument checks (messages under
+// the entry's name `who`), then the launch (route: which file's kernels)
+enum SetsRoute { SETS_FIXED, SETS_WIDE, SETS_WIDE_BILINEAR };  // rank_sets.hip, rank_sets_wide.hip, rank_sets_wide_bilinear.hip
+
+static int rank_sets_call(const char* who, SetsRoute route, int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld,
                           int64_t row_base, const float* source, int64_t S, int64_t ld_src, const int64_t* fixed_row,
                           const float* rel_emb, int64_t R, const int64_t* rel_id, const int64_t* true_row, int64_t q_head,
                           int64_t q_tail, const int64_t* set_ptr, const int64_t* set_row, int64_t nnz, int64_t G,
@@ -1115,10 +1117,16 @@ static int rank_sets_call(const char* who, bool wide, int model, const void* tab
                           void* workspace, size_t workspace_bytes, int device, void* stream) {
     if (!valid_model(model)) return fail(BLP_ERR_BAD_ARG, "%s: unknown model %d", who, model);
     if (!valid_table_dtype(table_dtype)) return fail(BLP_ERR_BAD_ARG, "%s: unknown table dtype %d", who, table_dtype);
+    const bool wide = route == SETS_WIDE;
+    if (route == SETS_WIDE_BILINEAR && !blp_rank_sets_wide_bilinear_supported(model, table_dtype, D))
+        return fail(BLP_ERR_UNSUPPORTED_DIM,
+                    "%s: model %d with table dtype %d at D = %d not supported (distmult / complex / simple, an f32 table, D %% 4 == 0, "
+                    "4 <= D <= 1024: see blp_rank_sets_wide_bilinear_supported)",
+                    who, model, table_dtype, D);
     if (wide && !blp_rank_sets_wide_supported(model, table_dtype, D))
         return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: model %d at D = %d not supported (transe, D %% 4 == 0, 4 <= D <= 1024: see blp_rank_sets_wide_supported)",
                     who, model, D);
-    if (!wide && !blp_rank_sets_supported(model, D))
+    if (route == SETS_FIXED && !blp_rank_sets_supported(model, D))
         return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (64 / 128 / 256: see blp_rank_sets_supported)", who, D);
     if (N < 0 || q_head < 0 || q_tail < 0 || ld < D || row_base < 0 || nnz < 0 || G < 0)
         return fail(BLP_ERR_BAD_ARG, "%s: negative size / row_base or ld < D (N=%lld q_head=%lld q_tail=%lld ld=%lld nnz=%lld G=%lld)", who,
@@ -1152,7 +1160,9 @@ static int rank_sets_call(const char* who, bool wide, int model, const void* tab
         spec.row_base = filter->row_base;
     }
     if (Q == 0) return BLP_OK;
-    const size_t need = wide ? blp::rank_sets_wide_workspace_bytes(D, q_head, q_tail, G) : blp::rank_sets_workspace_bytes(D, q_head, q_tail, G);
+    const size_t need = route == SETS_WIDE_BILINEAR ? blp::rank_sets_wide_bilinear_workspace_bytes(q_head, q_tail, G)
+                        : wide                      ? blp::rank_sets_wide_workspace_bytes(D, q_head, q_tail, G)
+                                                    : blp::rank_sets_workspace_bytes(D, q_head, q_tail, G);
     if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255u))
         return fail(BLP_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned and >= %zu bytes (got %zu)", who, need, workspace_bytes);
     DeviceGuard guard(device);
@@ -1160,11 +1170,11 @@ static int rank_sets_call(const char* who, bool wide, int model, const void* tab
     int cu = 0;
     if (int rc = compute_units(device, &cu)) return rc;
     const blp::SetLookup sets{set_ptr, set_row, qset_ptr_head, qset_ptr_tail, G, row_base};
-    hipError_t err = (wide ? blp::launch_rank_sets_wide : blp::launch_rank_sets)(model, D, table_dtype, table, N, ld, blp::QRows::rows_of(source, fixed_row, ld_src),
+    hipError_t err = (route == SETS_WIDE_BILINEAR ? blp::launch_rank_sets_wide_bilinear : wide ? blp::launch_rank_sets_wide : blp::launch_rank_sets)(model, D, table_dtype, table, N, ld, blp::QRows::rows_of(source, fixed_row, ld_src),
                                            blp::QRows::rows_of(rel_emb, rel_id, D), blp::QRows::rows_of(source, true_row, ld_src), q_head,
                                            q_tail, sets, nnz, spec, counts, workspace, cu, static_cast<hipStream_t>(stream));
     if (err != hipSuccess)
-        return hip_fail(err, wide ? "blp_rank_sets_wide launch" : table_dtype == BLP_DTYPE_F32 ? "blp_rank_sets launch" : "blp_rank_sets_typed launch");
+        return hip_fail(err, route == SETS_WIDE_BILINEAR ? "blp_rank_sets_wide_bilinear launch" : wide ? "blp_rank_sets_wide launch" : table_dtype == BLP_DTYPE_F32 ? "blp_rank_sets launch" : "blp_rank_sets_typed launch");
     return BLP_OK;
 }
 
@@ -1173,7 +1183,7 @@ int blp_rank_sets(int model, const float* table, int64_t N, int D, int64_t ld, i
                   const int64_t* true_row, int64_t q_head, int64_t q_tail, const int64_t* set_ptr, const int64_t* set_row, int64_t nnz,
                   int64_t G, const int64_t* qset_ptr_head, const int64_t* qset_ptr_tail, const blp_filter* filter, int32_t* counts,
                   void* workspace, size_t workspace_bytes, int device, void* stream) {
-    return rank_sets_call("blp_rank_sets", false, model, table, BLP_DTYPE_F32, N, D, ld, row_base, source, S, ld_src, fixed_row, rel_emb, R,
+    return rank_sets_call("blp_rank_sets", SETS_FIXED, model, table, BLP_DTYPE_F32, N, D, ld, row_base, source, S, ld_src, fixed_row, rel_emb, R,
                           rel_id, true_row, q_head, q_tail, set_ptr, set_row, nnz, G, qset_ptr_head, qset_ptr_tail, filter, counts,
                           workspace, workspace_bytes, device, stream);
 }
@@ -1192,7 +1202,7 @@ int blp_rank_sets_typed(int model, const void* table, int table_dtype, int64_t N
                         const int64_t* rel_id, const int64_t* true_row, int64_t q_head, int64_t q_tail, const int64_t* set_ptr,
                         const int64_t* set_row, int64_t nnz, int64_t G, const int64_t* qset_ptr_head, const int64_t* qset_ptr_tail,
                         const blp_filter* filter, int32_t* counts, void* workspace, size_t workspace_bytes, int device, void* stream) {
-    return rank_sets_call(table_dtype == BLP_DTYPE_F32 ? "blp_rank_sets" : "blp_rank_sets_typed", false, model, table, table_dtype, N, D, ld,
+    return rank_sets_call(table_dtype == BLP_DTYPE_F32 ? "blp_rank_sets" : "blp_rank_sets_typed", SETS_FIXED, model, table, table_dtype, N, D, ld,
                           row_base, source, S, ld_src, fixed_row, rel_emb, R, rel_id, true_row, q_head, q_tail, set_ptr, set_row, nnz, G,
                           qset_ptr_head, qset_ptr_tail, filter, counts, workspace, workspace_bytes, device, stream);
 }
@@ -1212,9 +1222,30 @@ int blp_rank_sets_wide(int model, const void* table, int table_dtype, int64_t N,
                        const int64_t* rel_id, const int64_t* true_row, int64_t q_head, int64_t q_tail, const int64_t* set_ptr,
                        const int64_t* set_row, int64_t nnz, int64_t G, const int64_t* qset_ptr_head, const int64_t* qset_ptr_tail,
                        const blp_filter* filter, int32_t* counts, void* workspace, size_t workspace_bytes, int device, void* stream) {
-    return rank_sets_call("blp_rank_sets_wide", true, model, table, table_dtype, N, D, ld, row_base, source, S, ld_src, fixed_row, rel_emb,
+    return rank_sets_call("blp_rank_sets_wide", SETS_WIDE, model, table, table_dtype, N, D, ld, row_base, source, S, ld_src, fixed_row, rel_emb,
                           R, rel_id, true_row, q_head, q_tail, set_ptr, set_row, nnz, G, qset_ptr_head, qset_ptr_tail, filter, counts,
                           workspace, workspace_bytes, device, stream);
+}
+
+// ---- candidate sets shared between queries, DistMult / ComplEx / SimplE at any width (rank_sets_wide_bilinear.hip)
+int blp_rank_sets_wide_bilinear_supported(int model, int table_dtype, int D) {
+    return valid_model(model) && blp::rank_sets_wide_bilinear_supported(model, table_dtype, D) ? 1 : 0;
+}
+
+size_t blp_rank_sets_wide_bilinear_workspace_bytes(int model, int table_dtype, int D, int64_t q_head, int64_t q_tail, int64_t G) {
+    if (!blp_rank_sets_wide_bilinear_supported(model, table_dtype, D) || q_head < 0 || q_tail < 0 || G < 0) return 0;
+    return blp::rank_sets_wide_bilinear_workspace_bytes(q_head, q_tail, G);
+}
+
+int blp_rank_sets_wide_bilinear(int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld, int64_t row_base,
+                                const float* source, int64_t S, int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R,
+                                const int64_t* rel_id, const int64_t* true_row, int64_t q_head, int64_t q_tail, const int64_t* set_ptr,
+                                const int64_t* set_row, int64_t nnz, int64_t G, const int64_t* qset_ptr_head,
+                                const int64_t* qset_ptr_tail, const blp_filter* filter, int32_t* counts, void* workspace,
+                                size_t workspace_bytes, int device, void* stream) {
+    return rank_sets_call("blp_rank_sets_wide_bilinear", SETS_WIDE_BILINEAR, model, table, table_dtype, N, D, ld, row_base, source, S, ld_src,
+                          fixed_row, rel_emb, R, rel_id, true_row, q_head, q_tail, set_ptr, set_row, nnz, G, qset_ptr_head, qset_ptr_tail,
+                          filter, counts, workspace, workspace_bytes, device, stream);
 }
 
 // ---- filtered top-k inside candidate sets shared between queries (topk_sets.hip)

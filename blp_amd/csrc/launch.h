@@ -66,6 +66,10 @@ hipError_t launch_rank_all_wide(int model, int D, const float* table, int64_t N,
                                 void* workspace, int n_cu, hipStream_t stream, hipEvent_t ev_start = nullptr,
                                 hipEvent_t ev_stop = nullptr);
 
+// rank_sets_wide_bilinear.hip: the same arithmetic inside candidate sets shared between queries (include/blp_hip.h:
+// blp_rank_sets_wide_bilinear).  Its launcher takes a SetLookup and is declared beside it and launch_rank_sets_wide, in
+// rank_common.h: rank_sets_wide_bilinear_supported, rank_sets_wide_bilinear_workspace_bytes, launch_rank_sets_wide_bilinear.
+
 // rank_all.hip: many passes of <= 4 + 4 queries back to back (one preparation and one finalisation launch for all of them)
 bool rank_static_passes_applicable(int model, int D, int64_t N, int64_t batch);
 size_t rank_static_passes_workspace_bytes(int D, int64_t n, int64_t batch);

@@ -25,6 +25,7 @@
 #include "rank_common.h"
 #include "score_core.h"
 #include "wide_bilinear.h"
+#include "wide_bilinear_keys.h"
 
 #pragma clang fp contract(off)
 
@@ -89,32 +90,7 @@ __global__ __launch_bounds__(kAwWaves * 64) void rank_all_wide_kernel(const floa
     }
 }
 
-// True-entity keys, eight lanes per query (wide_pair_score); the queries' accumulators start at zero.
-template <int MODEL>
-__global__ __launch_bounds__(256) void wide_bilinear_true_key_kernel(int D, const QRows q_fixed, const QRows q_rel, const QRows q_true,
-                                                                     int64_t q_head, int64_t Q, float* __restrict__ key_true,
-                                                                     unsigned long long* __restrict__ acc) {
-    const int sub = threadIdx.x & 7;
-    for (int64_t q0 = blockIdx.x * 32ll; q0 < Q; q0 += gridDim.x * 32ll) {  // workgroup-uniform
-        const int64_t qq = q0 + (threadIdx.x >> 3), q = qq < Q ? qq : Q - 1;
-        const float* e = q_true.row(q);
-        const float* f = q_fixed.row(q);
-        const float* r = q_rel.row(q);
-        const bool head = q0 + 31 < q_head ? true : (q0 >= q_head ? false : q < q_head);
-        float key;
-        if (q0 + 31 < q_head || q0 >= q_head) {  // wave-uniform side (all but the one group that straddles q_head)
-            key = head ? wide_pair_score<MODEL, HEAD>(e, f, r, D, sub) : wide_pair_score<MODEL, TAIL>(e, f, r, D, sub);
-        } else {  // both sides by every lane, each lane keeps its own
-            const float kh = wide_pair_score<MODEL, HEAD>(e, f, r, D, sub);
-            const float kt = wide_pair_score<MODEL, TAIL>(e, f, r, D, sub);
-            key = head ? kh : kt;
-        }
-        if (sub == 0 && qq < Q) {
-            key_true[qq] = key;
-            acc[qq] = 0;
-        }
-    }
-}
+// (wide_bilinear_true_key_kernel: wide_bilinear_keys.h, shared with rank_sets_wide_bilinear.hip)
 
 // Last kernel of a call (as rank_all.hip's filter_finalize_kernel, run-time width): a workgroup owns 64 queries, its
 // waves take the ones that have filter entries in turn (eight entries per step, eight lanes each: wide_pair_score), thread

@@ -141,6 +141,16 @@ hipError_t launch_rank_sets_wide(int model, int D, int dtype, const void* table,
                                  const QRows q_rel, const QRows q_true, int64_t q_head, int64_t q_tail, const SetLookup& sets,
                                  int64_t nnz, const FilterSpec& filter, int32_t* counts, void* workspace, int n_cu, hipStream_t stream);
 
+// rank_sets_wide_bilinear.hip: the same call for DistMult / ComplEx / SimplE at any width (D % 4 == 0, 4 <= D <= 1024;
+// include/blp_hip.h: blp_rank_sets_wide_bilinear), an f32 table: same arguments; the workspace holds the true keys, the
+// accumulators and two unit prefixes of G + 1 values, one per side -- independent of D
+bool rank_sets_wide_bilinear_supported(int model, int dtype, int D);
+size_t rank_sets_wide_bilinear_workspace_bytes(int64_t q_head, int64_t q_tail, int64_t G);
+hipError_t launch_rank_sets_wide_bilinear(int model, int D, int dtype, const void* table, int64_t N, int64_t ld, const QRows q_fixed,
+                                          const QRows q_rel, const QRows q_true, int64_t q_head, int64_t q_tail, const SetLookup& sets,
+                                          int64_t nnz, const FilterSpec& filter, int32_t* counts, void* workspace, int n_cu,
+                                          hipStream_t stream);
+
 // topk_sets.hip: filtered top-k inside candidate sets shared between queries (include/blp_hip.h: blp_topk_sets,
 // blp_topk_sets_typed); the table f32 or 16-bit (dtype: table_elem.h; ld in elements); the workspace -- the same for every
 // dtype -- holds the coefficient rows, the G + 1 values of the unit prefix and the (Q, S_max, k) partial lists

@@ -7,6 +7,7 @@ device memory and the stream; every arithmetic step of the hot path runs in the 
     rank_lists(...)     counts / scores of per-query candidate lists (only the listed rows are read)
     rank_sets(...)      counts against candidate sets shared by groups of queries (type-constrained evaluation)
     rank_sets_wide(...) the same for TransE at any width D % 4 == 0, 4 <= D <= 1024 (the BOW / DKRL 300 and 768)
+    rank_sets_wide_bilinear(...) the same for DistMult / ComplEx / SimplE at those widths, a float32 table
     topk_sets(...)      filtered top-k prediction inside candidate sets shared by groups of queries
     topk_sets_wide(...) the same for TransE at any width D % 4 == 0, 4 <= D <= 1024 (the BOW / DKRL 300 and 768)
     rerank_cosine(...)  cosine of every retrieval candidate with its query (retrieval.py:170-175)
@@ -613,10 +614,38 @@ def rank_sets_wide(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head
                       qset_ptr_tail, filter, row_base, out)
 
 
+def rank_sets_wide_bilinear_supported(rel_model, dim, dtype=torch.float32):
+    """True if rank_sets_wide_bilinear takes this model, width and table dtype (blp_rank_sets_wide_bilinear_supported: distmult,
+    complex or simple, D % 4 == 0, 4 <= D <= 1024, a float32 table)."""
+    if dtype not in TABLE_DTYPES:
+        return False
+    return bool(_lib.lib().blp_rank_sets_wide_bilinear_supported(_lib.MODEL_IDS[rel_model], TABLE_DTYPES[dtype], int(dim)))
+
+
+def rank_sets_wide_bilinear_workspace_bytes(rel_model, D, q_head, q_tail, num_sets, dtype=torch.float32):
+    """Bytes of rank_sets_wide_bilinear's workspace: true keys, accumulators and two unit prefixes of num_sets + 1 offsets,
+    whatever the width, the table's length and the sets' sizes (0: not supported, or a negative size)."""
+    if dtype not in TABLE_DTYPES:
+        return 0
+    return int(_lib.lib().blp_rank_sets_wide_bilinear_workspace_bytes(_lib.MODEL_IDS[rel_model], TABLE_DTYPES[dtype], int(D), int(q_head),
+                                                                     int(q_tail), int(num_sets)))
+
+
+def rank_sets_wide_bilinear(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, true_row, set_ptr, set_row, qset_ptr_head,
+                            qset_ptr_tail, filter=None, row_base=0, out=None):
+    """rank_sets for DistMult / ComplEx / SimplE at any width D % 4 == 0, 4 <= D <= 1024 on a float32 table
+    (blp_rank_sets_wide_bilinear: eight lanes per set row, the coefficients of a chunk of 8 queries of the set's group in LDS --
+    rank_all_wide's sum order on gathered rows): same arguments, same counts -- the reference's bit for bit."""
+    return _rank_sets("bilinear", rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, true_row, set_ptr, set_row, qset_ptr_head,
+                      qset_ptr_tail, filter, row_base, out)
+
+
 def _rank_sets(wide, rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, true_row, set_ptr, set_row, qset_ptr_head,
                qset_ptr_tail, filter, row_base, out):
-    """rank_sets (blp_rank_sets_typed) and rank_sets_wide (blp_rank_sets_wide): one argument handling, two entries."""
-    who = "rank_sets_wide" if wide else "rank_sets"
+    """rank_sets (blp_rank_sets_typed), rank_sets_wide (blp_rank_sets_wide) and rank_sets_wide_bilinear
+    (blp_rank_sets_wide_bilinear; ``wide`` == "bilinear"): one argument handling, three entries."""
+    bilinear = wide == "bilinear"
+    who = "rank_sets_wide_bilinear" if bilinear else "rank_sets_wide" if wide else "rank_sets"
     _require_device(table, source, fixed_row, rel_emb, rel_ids, true_row, set_ptr, set_row, qset_ptr_head, qset_ptr_tail)
     if table.dtype not in TABLE_DTYPES:
         raise TypeError(f"{who} reads a float32, float16 or bfloat16 table, got {table.dtype}")
@@ -639,7 +668,10 @@ def _rank_sets(wide, rel_model, table, source, fixed_row, rel_emb, rel_ids, q_he
         raise ValueError("set_ptr, qset_ptr_head and qset_ptr_tail need G + 1 entries each")
     if not 0 <= q_head <= Q:
         raise ValueError(f"q_head = {q_head} outside [0, {Q}]")
-    if wide and not rank_sets_wide_supported(rel_model, D, table.dtype):
+    if bilinear and not rank_sets_wide_bilinear_supported(rel_model, D, table.dtype):
+        raise ValueError(f"rank_sets_wide_bilinear: {rel_model} with a {table.dtype} table at D = {D} not supported (distmult / complex / "
+                         "simple, a float32 table, D % 4 == 0, 4 <= D <= 1024: see rank_sets_wide_bilinear_supported)")
+    if wide and not bilinear and not rank_sets_wide_supported(rel_model, D, table.dtype):
         raise ValueError(f"rank_sets_wide: {rel_model} at D = {D} not supported (transe, D % 4 == 0, 4 <= D <= 1024: see rank_sets_wide_supported)")
     if not wide and not rank_sets_supported(rel_model, D, table.dtype):
         raise ValueError(f"rank_sets: D = {D} not supported (64 / 128 / 256: see rank_sets_supported)")
@@ -655,17 +687,18 @@ def _rank_sets(wide, rel_model, table, source, fixed_row, rel_emb, rel_ids, q_he
     model = _lib.MODEL_IDS[rel_model]
     stream = torch._C._cuda_getCurrentRawStream(dev.index)
     tdt = TABLE_DTYPES[table.dtype]
-    ws_bytes = (L.blp_rank_sets_wide_workspace_bytes if wide else L.blp_rank_sets_typed_workspace_bytes)(model, tdt, D, q_head, Q - q_head, G)
+    entry = "blp_rank_sets_wide_bilinear" if bilinear else "blp_rank_sets_wide" if wide else "blp_rank_sets_typed"
+    ws_bytes = getattr(L, entry + "_workspace_bytes")(model, tdt, D, q_head, Q - q_head, G)
     workspace = _workspace(dev, stream, ws_bytes)
     spec = None if filter is None else _filter_spec(filter, Q, dev)
-    status = (L.blp_rank_sets_wide if wide else L.blp_rank_sets_typed)(model, table.data_ptr(), tdt, N, D, table.stride(0) if tdt or N > 1 else D, int(row_base),
+    status = getattr(L, entry)(model, table.data_ptr(), tdt, N, D, table.stride(0) if tdt or N > 1 else D, int(row_base),
                                    source.data_ptr(), source.shape[0], source.stride(0) if source.shape[0] > 1 else D,
                                    fixed_row.data_ptr(), rel_emb.data_ptr(), rel_emb.shape[0], rel_ids.data_ptr(), true_row.data_ptr(),
                                    q_head, Q - q_head, set_ptr.data_ptr(), _addr(set_row) if nnz else None, nnz, G,
                                    qset_ptr_head.data_ptr(), qset_ptr_tail.data_ptr(), spec, counts.data_ptr(), workspace.data_ptr(),
                                    ws_bytes, dev.index, stream)
     if status:
-        _lib.check(status, "blp_rank_sets_wide" if wide else "blp_rank_sets_typed" if tdt else "blp_rank_sets")
+        _lib.check(status, entry if wide or tdt else "blp_rank_sets")
     return counts
 
 

@@ -1235,8 +1235,10 @@ def rank_in_sets(model, table, triples, sets, ent2idx, *, set_ids=None, side="bo
     set is fetched once per chunk of 128 queries of its group; a 16-bit table is read as it is, only the Q fixed and the Q true
     rows are gathered and widened).  A HIP table at any other width blp_rank_sets_wide takes -- TransE, D % 4 == 0, 4 <= D <= 1024:
     the BOW / DKRL 300 and 768 -- goes through blp_rank_sets_wide (a row of a set fetched once per chunk of 16 queries of its
-    group; the same counts, a 16-bit table handled the same way).  CPU tensors, and the bilinear models at other widths, take the
-    dense route: score_fn on gathered rows."""
+    group; the same counts, a 16-bit table handled the same way).  A float32 HIP table of DistMult / ComplEx / SimplE at those
+    widths goes through blp_rank_sets_wide_bilinear (a row of a set fetched once per chunk of 8 queries of one side of its
+    group; the same counts).  CPU tensors, and 16-bit tables of the bilinear models at other widths than 64 / 128 / 256, take
+    the dense route: score_fn on gathered rows."""
     model = _module(model)
     if side not in ("head", "tail", "both"):
         raise ValueError(f"side must be 'head', 'tail' or 'both', got {side!r}")
@@ -1288,6 +1290,8 @@ def rank_in_sets(model, table, triples, sets, ent2idx, *, set_ids=None, side="bo
         fused = ops.rank_sets
     elif table.is_cuda and ops.rank_sets_wide_supported(model.rel_model, D, table.dtype):
         fused = ops.rank_sets_wide
+    elif table.is_cuda and ops.rank_sets_wide_bilinear_supported(model.rel_model, D, table.dtype):
+        fused = ops.rank_sets_wide_bilinear
     if fused is not None:
         if table.dtype != torch.float32:
             # float32 query vectors: the Q fixed rows, then the Q true rows, gathered and widened (exact) by the library's own

@@ -672,6 +672,29 @@ int blp_rank_sets_wide(int model, const void *table, int table_dtype, int64_t N,
                        const int64_t *set_row, int64_t nnz, int64_t G, const int64_t *qset_ptr_head,
                        const int64_t *qset_ptr_tail, const blp_filter *filter, int32_t *counts, void *workspace,
                        size_t workspace_bytes, int device, void *stream);
+/* Candidate sets shared between queries for DistMult / ComplEx / SimplE at ANY width: blp_rank_sets_wide_bilinear is
+ * blp_rank_sets_wide -- the same argument list in the same order and the contract above word for word (the sets CSR, row_base
+ * shards, the grouping, the filter and true-entity rules, the (Q, 4) int32 counts, the reference's bit for bit) -- for the three
+ * bilinear models at the widths blp_rank_sets_supported refuses.  The sum order is blp_rank_all_wide's (eight lanes per set
+ * row, the coefficients of a chunk of 8 queries of the set's group in LDS: rank_sets_wide_bilinear.hip): a row of a set is
+ * fetched once per (set, chunk of 8 queries of one side of its group).
+ * Limits (blp_rank_sets_wide_bilinear_supported): BLP_MODEL_DISTMULT / COMPLEX / SIMPLE, table_dtype BLP_DTYPE_F32 only (the
+ * argument is there for 16-bit tables to follow), D % 4 == 0 and 4 <= D <= 1024 -- 64 / 128 / 256 included, where it is a
+ * second implementation of the same bits (blp_rank_sets is the faster one); everything else answers 0.  The other limits, the
+ * alignment rules, the status codes and the messages are blp_rank_sets_wide's (one argument-checking path).
+ * Workspace: blp_rank_sets_wide_bilinear_workspace_bytes(model, table_dtype, D, q_head, q_tail, G) bytes (0 where unsupported
+ * or a size is negative), 256-B aligned: true keys (4 Q bytes), accumulators (8 Q) and two unit prefixes of G + 1 int64, one
+ * per side -- independent of N, nnz and D.
+ * Asynchronous on `stream`, no host synchronisation, no allocation.  Deterministic: integer adds only, nothing depends on the
+ * grid.  (Added after 6.0.0 without a version change: no existing entry point changed.) */
+int blp_rank_sets_wide_bilinear_supported(int model, int table_dtype, int D);
+size_t blp_rank_sets_wide_bilinear_workspace_bytes(int model, int table_dtype, int D, int64_t q_head, int64_t q_tail, int64_t G);
+int blp_rank_sets_wide_bilinear(int model, const void *table, int table_dtype, int64_t N, int D, int64_t ld, int64_t row_base,
+                                const float *source, int64_t S, int64_t ld_src, const int64_t *fixed_row, const float *rel_emb,
+                                int64_t R, const int64_t *rel_id, const int64_t *true_row, int64_t q_head, int64_t q_tail,
+                                const int64_t *set_ptr, const int64_t *set_row, int64_t nnz, int64_t G,
+                                const int64_t *qset_ptr_head, const int64_t *qset_ptr_tail, const blp_filter *filter,
+                                int32_t *counts, void *workspace, size_t workspace_bytes, int device, void *stream);
 
 /* --------------------------------------------------------------------------------------------
  * Filtered top-k INSIDE candidate sets shared between queries: ANSWER a query (h, r, ?) / (?, r, t) with the k rows of ITS SET

@@ -8,7 +8,7 @@ then --steps steps; one JSON line with the median and p90 of both, their ratio a
 call (rows fetched: one per set entry and chunk of 128 queries of its group, D x 4 bytes each).
 
     python tools/rank_sets_bench.py [--steps 30] [--warmup 3] [--only NAME ...] [--out FILE.jsonl] [--table16 {f16,bf16}]
-                                    [--width D [D ...]] [--repeats 5]
+                                    [--width D [D ...]] [--repeats 5] [--model {distmult,complex,simple}]
 
 --table16: the table rounded to IEEE half / bfloat16 instead; blp_rank_sets_typed on the 16-bit table alternates with
 blp_rank_sets on that table widened to f32 (the yardstick), counts required equal first; one JSON line with both medians,
@@ -19,6 +19,13 @@ width D (105 740 queries, 474 sets, 14 541 rows).  At the widths blp_rank_sets t
 blp_rank_sets, elsewhere (300, 768) with blp_rank_lists on the expanded lists; counts required equal first; --repeats
 measurements of --steps steps each, one JSON line with the median of the medians of both routes, their ratio and the spread of
 the repeated medians ((max - min) / median).
+
+--model {distmult,complex,simple} (with --width): blp_rank_sets_wide_bilinear -- these models at any width, an f32 table -- on the
+same shape.  Its counts must equal those of the dense route (ranking._rank_sets_dense: score_fn on gathered rows, what
+rank_in_sets took for these shapes before) and, at the widths blp_rank_lists takes these models (64 / 128 / 256), those of
+blp_rank_lists on the expanded lists; then the routes alternate step by step, and one JSON line has the median of the repeated
+medians of each with its spread, the ratios to the new call, and whether the new call is faster than the dense route by more
+than both spreads together.  At 64 / 128 / 256 blp_rank_sets is timed as well (for the record: it keeps those widths).
 
   fb15k237-{transe,distmult}   105 740 queries, 14 541 x 128 table, 474 sets of 50 .. 8 000 rows (log-uniform)
   longtable-transe             13 788 queries, 4.6 M x 128 table, 1 644 sets of 10^3 .. 10^6 rows (log-uniform)
@@ -253,6 +260,56 @@ def run_wide(D, steps, warmup, repeats, table16=None):
             "pairs_per_s": round(pairs / (a["median_ms"] * 1e-3), 0), "steps": steps, "warmup": warmup, "repeats": repeats}
 
 
+def run_wide_bilinear(model, D, steps, warmup, repeats):
+    """blp_rank_sets_wide_bilinear at width D on the fb15k237 shape, next to the dense route and, where they take the shape, to
+    blp_rank_lists on the expanded lists and to blp_rank_sets."""
+    from blp_amd import models, ranking
+    cfg = dict(WORKLOADS["fb15k237-distmult"], model=model, D=int(D))
+    w = make_workload(cfg)
+    Q, table, filt = cfg["Q"], w["table"], w["filt"]
+    sets_args = (w["rel_w"], w["rel_ids"], w["q_head"], w["true"], w["set_ptr"], w["set_row"], w["qh"], w["qt"])
+    got = {name: torch.empty_like(w["counts"]) for name in ("wide_bilinear", "dense", "expanded_lists", "rank_sets")}
+    module = models.LinkPrediction(int(D), model, "margin", w["rel_w"].shape[0], 0)
+    dense_filt = (filt.seg_lo, filt.seg_hi, filt.values, filt.exclude, filt.ent2idx)
+
+    def wide_bilinear():
+        ops.rank_sets_wide_bilinear(model, table, table, w["fixed"], *sets_args, filter=filt, out=got["wide_bilinear"])
+
+    def dense():  # the gathers of the query vectors are part of the route, as in ranking.rank_in_sets
+        got["dense"] = ranking._rank_sets_dense(module.score_fn, table, table[w["fixed"]].float(), w["rel_w"][w["rel_ids"]],
+                                                table[w["true"]].float(), w["q_head"], w["set_ptr"], w["set_row"], w["qh"], w["qt"], 0,
+                                                dense_filt)
+
+    calls = {"wide_bilinear": wide_bilinear, "dense": dense}
+    if ops.rank_lists_supported(model, D, table.dtype):
+        lists, _ = expanded_calls(w, Q)  # outside the timing
+
+        def expanded_lists():
+            for a, b, ptr, rows, part in lists:
+                ops.rank_lists(model, table, table, w["fixed"][a:b], w["rel_w"], w["rel_ids"][a:b], min(max(w["q_head"] - a, 0), b - a), ptr,
+                               rows, true_row=w["true"][a:b], filter=part, out=(got["expanded_lists"][a:b], None))
+
+        calls["expanded_lists"] = expanded_lists
+    if ops.rank_sets_supported(model, D, table.dtype):
+        calls["rank_sets"] = lambda: ops.rank_sets(model, table, table, w["fixed"], *sets_args, filter=filt, out=got["rank_sets"])
+    with torch.no_grad():
+        for fn in calls.values():
+            fn()
+        equal = {name: bool(torch.equal(got["wide_bilinear"], got[name])) for name in calls if name != "wide_bilinear"}
+        head = {"workload": f"fb15k237-{model}-wide-{D}", **cfg, "counts_equal": equal,
+                "not_timed": [n for n in ("expanded_lists", "rank_sets") if n not in calls]}
+        assert all(equal.values()), head
+        runs = [measure(calls, steps, warmup) for _ in range(repeats)]
+    rec = {name: repeated(runs, name) for name in calls}
+    new = rec["wide_bilinear"]
+    ratios = {f"{name}_over_wide_bilinear": round(rec[name]["median_ms"] / new["median_ms"], 3) for name in calls if name != "wide_bilinear"}
+    faster = bool(rec["dense"]["median_ms"] * (1 - rec["dense"]["spread"]) > new["median_ms"] * (1 + new["spread"]))
+    pairs = int(w["n_per"].sum())
+    return {**head, "set_entries": int(w["set_row"].numel()), "pairs": pairs, "filter_entries_per_query": FILTER_PER_QUERY,
+            **{f"{name}_ms": r for name, r in rec.items()}, **ratios, "faster_than_dense_by_more_than_both_spreads": faster,
+            "pairs_per_s": round(pairs / (new["median_ms"] * 1e-3), 0), "steps": steps, "warmup": warmup, "repeats": repeats}
+
+
 def emit(line, out):
     print(line, flush=True)
     if out:
@@ -272,7 +329,15 @@ def main():
     ap.add_argument("--table16", choices=("f16", "bf16"))
     ap.add_argument("--width", type=int, nargs="+", help="blp_rank_sets_wide at these widths on the fb15k237-transe shape")
     ap.add_argument("--repeats", type=int, default=5, help="with --width: measurements whose medians' spread is reported")
+    ap.add_argument("--model", choices=("distmult", "complex", "simple"),
+                    help="with --width: blp_rank_sets_wide_bilinear for this model instead of blp_rank_sets_wide for TransE")
     args = ap.parse_args()
+    if args.model and (not args.width or args.table16):
+        ap.error("--model goes with --width and an f32 table")
+    if args.model:
+        for D in args.width:
+            emit(json.dumps(run_wide_bilinear(args.model, D, args.steps, args.warmup, args.repeats)), args.out)
+        return
     for D in args.width or ():
         emit(json.dumps(run_wide(D, args.steps, args.warmup, args.repeats, args.table16)), args.out)
     if args.width:
