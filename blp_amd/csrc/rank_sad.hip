@@ -32,12 +32,16 @@
 //           which otherwise find the list empty.  Flagged segments go to the same launch's sweep workgroups.
 // Non-finite values anywhere, or a degenerate range, make every kernel of the pre-pass a no-op and the
 // segment refinement sweep all tiles: the result is exact in every case, just slower.
+//   filter  (filtered setting) the rows a query's filter removes are re-scored against the true entity by extra workgroups at
+//           the end of the first pre-pass launch (sad_filter_role) -- gather latency under the pre-pass's VALU work -- and
+//           subtracted by sad_finalize_kernel, one thread per query; without a filter: finalize_counts_kernel as everywhere.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include "exact_coop.h"
+#include "filter_finalize.h"
 #include "knobs.h"
 #include "launch.h"
 #include "rank_common.h"
@@ -65,6 +69,7 @@ __global__ __launch_bounds__(256) void sad_prelude_kernel(const float* __restric
                                                           const QRows q_true, const QRows q_fixed, const QRows q_rel,
                                                           int64_t q_head, int64_t Q, unsigned query_blocks,
                                                           float* __restrict__ key_true, unsigned long long* __restrict__ acc,
+                                                          unsigned long long* __restrict__ removed,
                                                           SadParams* __restrict__ partial) {
     SadRange range;
     if (blockIdx.x < query_blocks) {
@@ -77,7 +82,7 @@ __global__ __launch_bounds__(256) void sad_prelude_kernel(const float* __restric
             const bool head = q < q_head;
             auto seen = [&](float f, float r) { if (live) range.see(sad_coef(f, r, head)); };
             const float key = transe_key_64_rt(q_true.row(q), q_fixed.row(q), q_rel.row(q), D, head, slab[wave], lane, seen);
-            if (live) { key_true[q] = key; acc[q] = 0; }
+            if (live) { key_true[q] = key; acc[q] = 0; removed[q] = 0; }  // (removed: the pre-pass launch's filter role)
         }
     } else {
         const int64_t stride = (int64_t)(gridDim.x - query_blocks) * 256;
@@ -260,6 +265,90 @@ extern "C" int blp_debug_read_sad_timing(unsigned long long* out) {
 }
 #endif
 
+// The filter role of the pre-pass launch (filtered setting, first candidate slab): the workgroups after the launch's pre-pass
+// workgroups do the front half of filter_finalize_kernel (filter_finalize.h) -- the rows the filter removes, re-scored against
+// the true entity -- which needs key_true and the caller's inputs only, nothing the pre-pass computes.  It is all gather
+// latency (a few tens of thousands of entries on the FB15k-237 block, three 512-byte rows each) next to a VALU-bound pre-pass
+// whose memory system idles, and the role's workgroups are the grid's last: they run in the launch's tail, where the compute
+// units hold fewer than five workgroups.  A role workgroup owns runs of kSweepQueries queries, grid-strided: the first wave
+// scans the run's segment lengths, the entries are numbered across the run and found by binary search in the scan, one entry
+// per lane and trip through transe_key_lane (true_key_kernel's keys bit for bit, no LDS slab), counted per query in LDS as
+// gt | ge << 32; a query that has something removed gets one plain store into removed[] (zeroed by the prelude; a query
+// belongs to one run, a run to one workgroup).  Same entry semantics as filter_finalize_kernel: filter_row (exclude, ent2idx,
+// row_base, rows outside [0, N)), replaces_head, hi < lo an empty segment.  sad_finalize_kernel subtracts removed[] at the end.
+// LDS: 1 800 bytes carved from the pre-pass's pair_s (the kernel's static LDS does not grow).
+//
+// Role workgroups at most.  ms per step of the FB15k-237 block (1 653 runs of 64 queries, 23 598 pre-pass workgroups; one box,
+// fresh process per 100-step sample; profiles/sad_filter_role/role_grid_scan.log and step_ab_fb15k237-transe.log; the parent
+// without the role: 2.993 .. 3.013): 128: 2.959 | 2.972 | 2.960, 512: 2.965 | 2.963 | 2.960 | 2.962 | 2.965, 2 048 (a workgroup
+// per run): 2.969 | 2.974 | 2.959.  The samples of one value differ by more (0.012) than the values' means (0.003): from 128 to
+// a workgroup per run the data do not choose, the role is hidden at every one of them.  512 keeps the grid's tail short on
+// blocks with many more runs without leaving a role workgroup more than four runs on this one.
+#ifndef BLP_SAD_FILTER_BLOCKS
+#define BLP_SAD_FILTER_BLOCKS 512
+#endif
+constexpr unsigned kSFilterRoleBlocks = BLP_SAD_FILTER_BLOCKS;
+constexpr size_t kSFilterRoleLds = (kSweepQueries + 2) * sizeof(int) + kSweepQueries * (sizeof(unsigned long long) + 2 * sizeof(const float*));
+
+template <int D>
+__device__ __forceinline__ void sad_filter_role(unsigned vblock, unsigned vgrid, char* lds, const float* __restrict__ table, int64_t N,
+                                                int64_t ld, const QRows& q_fixed, const QRows& q_rel, const float* __restrict__ key_true,
+                                                int64_t q_head, int64_t Q, const FilterSpec& filter,
+                                                unsigned long long* __restrict__ removed) {
+    int* prefix = reinterpret_cast<int*>(lds);                                                             // [kSweepQueries + 1] (+ 1: alignment)
+    unsigned long long* rem_s = reinterpret_cast<unsigned long long*>(lds + (kSweepQueries + 2) * sizeof(int));  // [kSweepQueries]
+    const float** frow = reinterpret_cast<const float**>(rem_s + kSweepQueries);  // the queries' two vectors: looked up once,
+    const float** rrow = frow + kSweepQueries;                                    // not once per entry
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t n_runs = (Q + kSweepQueries - 1) / kSweepQueries;
+    for (int64_t run = vblock; run < n_runs; run += vgrid) {  // workgroup-uniform
+        const int64_t q_base = run * kSweepQueries;
+        if (threadIdx.x < 64) {
+            const int64_t q = q_base + lane;
+            frow[lane] = q_fixed.row(q < Q ? q : 0);
+            rrow[lane] = q_rel.row(q < Q ? q : 0);
+            int n = q < Q ? (int)(filter.hi[q] - filter.lo[q]) : 0;
+            n = n > 0 ? n : 0;
+            rem_s[lane] = 0;
+            int incl = n;  // inclusive scan over the wave
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const int up = __shfl_up(incl, off);
+                if (lane >= off) incl += up;
+            }
+            prefix[lane + 1] = incl;
+            if (lane == 0) prefix[0] = 0;
+        }
+        __syncthreads();
+        const int total = prefix[kSweepQueries];
+        for (int x0 = wave * 64; x0 < total; x0 += kSW * 64) {  // wave-uniform
+            const int x = x0 + lane;
+            int64_t q = q_base, row = -1;
+            int slot = 0;
+            if (x < total) {
+                int lo = 0, hi = kSweepQueries;  // largest slot with prefix[slot] <= x
+#pragma unroll
+                for (int step = 0; step < 6; ++step) {
+                    const int mid = (lo + hi) >> 1;
+                    if (prefix[mid] <= x) lo = mid; else hi = mid;
+                }
+                slot = lo;
+                q = q_base + slot;
+                row = filter_row(filter, q, filter.lo[q] + (x - prefix[slot]), N);
+            }
+            const bool live = row >= 0;  // (idle lanes and entries that remove nothing: row 0 and the run's first query along)
+            const float key = transe_key_lane<D>(table + (live ? row : 0) * ld, frow[slot], rrow[slot], replaces_head(q, q_head, Q, 0));
+            const float kt = key_true[q];
+            const unsigned long long gt = live && key > kt, ge_ = live && key >= kt;
+            if (gt | ge_) atomicAdd(&rem_s[slot], gt | (ge_ << 32));
+        }
+        __syncthreads();
+        if (threadIdx.x < 64 && q_base + lane < Q && rem_s[lane]) removed[q_base + lane] = rem_s[lane];
+        // (the next run's first stores to prefix / rem_s / frow come from this same wave, after the barrier above)
+    }
+}
+
+// Grid: n_prepass = n_groups x chunks pre-pass workgroups, then (first slab of a filtered call only) the filter role's.
 template <int D, int TPW>
 __global__ __launch_bounds__(kSW * 64, (TPW * D / 2 <= 64 ? 5 : TPW * D / 2 <= 128 ? 3 : 2)) void rank_sad_kernel(
     const uint4* __restrict__ cimg, const unsigned* __restrict__ resid, int64_t n_rows, int n_groups, int q_per_group,
@@ -267,15 +356,22 @@ __global__ __launch_bounds__(kSW * 64, (TPW * D / 2 <= 64 ? 5 : TPW * D / 2 <= 1
     unsigned long long* __restrict__ acc,
     unsigned* __restrict__ flags, uint2* __restrict__ pairs, SadParams* __restrict__ params,
     const float* __restrict__ table, int64_t ld, const QRows q_fixed, const QRows q_rel, int64_t q_head,
-    const float* __restrict__ key_true) {
-    if (!sad_scale(params).ok) return;
-#ifdef BLP_TIMING
-    const unsigned long long clk0 = __builtin_readcyclecounter(), wall0 = __builtin_amdgcn_s_memrealtime();
-#endif
+    const float* __restrict__ key_true, unsigned n_prepass, const FilterSpec filter, int64_t n_table,
+    unsigned long long* __restrict__ removed) {
     __shared__ int2 thr_s[kSChunk];
     __shared__ unsigned cnt[kSChunk];
     __shared__ uint2 pair_s[kSQuota];
     __shared__ unsigned wave_used[kSW], wave_base[kSW], ec_max_s;  // per-wave slices of pair_s: fill counts, global offsets
+    static_assert(kSFilterRoleLds <= sizeof(uint2) * kSQuota, "the filter role's arrays alias pair_s");
+    if (blockIdx.x >= n_prepass) {  // before the pre-pass's off-switch: a degenerate range or a non-finite value must not skip the filter
+        sad_filter_role<D>(blockIdx.x - n_prepass, gridDim.x - n_prepass, reinterpret_cast<char*>(pair_s), table, n_table, ld, q_fixed,
+                           q_rel, key_true, q_head, Q, filter, removed);
+        return;
+    }
+    if (!sad_scale(params).ok) return;
+#ifdef BLP_TIMING
+    const unsigned long long clk0 = __builtin_readcyclecounter(), wall0 = __builtin_amdgcn_s_memrealtime();
+#endif
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
@@ -285,7 +381,8 @@ __global__ __launch_bounds__(kSW * 64, (TPW * D / 2 <= 64 ? 5 : TPW * D / 2 <= 1
     // XCD now walks a contiguous range of a logical index laid out as (block of kSadChunkBlock query chunks) x (candidate
     // group) x (chunk of the block): a query chunk's image is read by one XCD only, the candidate image once per block
     // of chunks.
-    const unsigned n_blocks = gridDim.x, xcd = blockIdx.x & 7u, per_xcd = n_blocks >> 3, rem_b = n_blocks & 7u;
+    // (n_prepass, not gridDim.x: the filter role's workgroups follow the pre-pass's.)
+    const unsigned n_blocks = n_prepass, xcd = blockIdx.x & 7u, per_xcd = n_blocks >> 3, rem_b = n_blocks & 7u;
     const unsigned logical = (xcd < rem_b ? xcd * (per_xcd + 1) : rem_b * (per_xcd + 1) + (xcd - rem_b) * per_xcd) + (blockIdx.x >> 3);
     const unsigned n_chunks_all = n_blocks / (unsigned)n_groups;  // the grid is n_groups x chunks
     const unsigned per_cb = (unsigned)n_groups * kSadChunkBlock, cb = logical / per_cb, in_cb = logical % per_cb;
@@ -566,12 +663,25 @@ __global__ __launch_bounds__(256) void sad_refine_kernel(const float* __restrict
     }
 }
 
+// Last kernel of a filtered call on this path, one thread per query: the filter role of the first pre-pass launch left what the
+// filter removes in removed[], so all that remains is the unpack (acc has one slot here: no sum over partial results, no LDS).
+__global__ __launch_bounds__(256) void sad_finalize_kernel(const unsigned long long* __restrict__ acc,
+                                                           const unsigned long long* __restrict__ removed, int64_t Q,
+                                                           int32_t* __restrict__ counts) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= Q) return;
+    const unsigned long long a = acc[q], r = removed[q];
+    const int32_t gt = (int32_t)(a & 0xffffffffull), ge = (int32_t)(a >> 32);
+    reinterpret_cast<int4*>(counts)[q] = make_int4(gt, ge, gt - (int32_t)(r & 0xffffffffull), ge - (int32_t)(r >> 32));
+}
+
 // ------------------------------------------------------------------------------------------------
 static constexpr int sad_tiles_per_wave(int D) { return D <= 64 ? 2 : 1; }
 
 struct SadWorkspace {
     float* key_true;
     unsigned long long* acc;
+    unsigned long long* removed;  // per query, packed like acc: what the filter removes above / at least the true entity
     SadParams* params; SadParams* partial; int2* thr; unsigned* qimg; uint4* cimg; unsigned* resid; unsigned* flags;
     uint2* pairs;
     float* fallback_coef;  // coefficient rows of the exact re-ranking (rank_common.h: Gate), or nullptr: this block has no fallback
@@ -628,6 +738,7 @@ static SadWorkspace carve_sad(void* base, int D, int64_t N, int64_t q_head, int6
     size_t off = 0;
     w.key_true = reinterpret_cast<float*>(p + off);  off = align_up(off + (size_t)Q * 4, 256);
     w.acc = reinterpret_cast<unsigned long long*>(p + off);   off = align_up(off + (size_t)Q * 8, 256);
+    w.removed = reinterpret_cast<unsigned long long*>(p + off); off = align_up(off + (size_t)Q * 8, 256);
     w.params = reinterpret_cast<SadParams*>(p + off); off = align_up(off + sizeof(SadParams), 256);
     w.partial = reinterpret_cast<SadParams*>(p + off); off = align_up(off + sizeof(SadParams) * kSRangeBlocks, 256);
     w.thr = reinterpret_cast<int2*>(p + off);         off = align_up(off + (size_t)Q * 8, 256);
@@ -710,7 +821,7 @@ static hipError_t rank_sad_impl(const float* table, int64_t N, int64_t ld, const
     range_blocks = range_blocks < kSPreludeTableBlocks ? (range_blocks > 0 ? range_blocks : 1) : kSPreludeTableBlocks;
     const int n_partial = (int)(key_blocks + range_blocks);
     sad_prelude_kernel<D><<<dim3((unsigned)n_partial), 256, 0, stream>>>(table, N, ld, q_true, q_fixed, q_rel, q_head, Q,
-                                                                         (unsigned)key_blocks, w.key_true, w.acc, w.partial);
+                                                                         (unsigned)key_blocks, w.key_true, w.acc, w.removed, w.partial);
     // the first slab's flag bitmap and pair counter are zeroed by the prep kernels (later slabs: memsets)
     const int64_t first_rows = N < w.pass_groups * kSW * TPW * 64 ? N : w.pass_groups * kSW * TPW * 64;
     const int64_t first_groups = ((first_rows + 63) / 64 + kSW * TPW - 1) / (kSW * TPW);
@@ -737,9 +848,17 @@ static hipError_t rank_sad_impl(const float* table, int64_t N, int64_t ld, const
             if (err != hipSuccess) return err;
         }
         const float* slab = table + slab0 * ld;
-        rank_sad_kernel<D, TPW><<<dim3((unsigned)n_blocks), kSW * 64, 0, stream>>>(
+        // the filter role (sad_filter_role): after the first slab's pre-pass workgroups, a workgroup per run of kSweepQueries
+        // queries up to kSFilterRoleBlocks; it reads the whole table (slab0 == 0: `slab` is `table`)
+        int64_t role_blocks = 0;
+        if (filter.on() && slab0 == 0) {
+            role_blocks = (Q + kSweepQueries - 1) / kSweepQueries;
+            role_blocks = role_blocks < (int64_t)kSFilterRoleBlocks ? role_blocks : (int64_t)kSFilterRoleBlocks;
+        }
+        if (n_blocks + role_blocks > 0x7fffffff) return hipErrorInvalidValue;
+        rank_sad_kernel<D, TPW><<<dim3((unsigned)(n_blocks + role_blocks)), kSW * 64, 0, stream>>>(
             w.cimg + (slab0 / 64) * (D / 8) * 64, w.resid + slab0, n_rows, (int)n_groups, per_group, w.qimg, w.thr, Q, words, w.acc,
-            w.flags, w.pairs, w.params, slab, ld, q_fixed, q_rel, q_head, w.key_true);
+            w.flags, w.pairs, w.params, slab, ld, q_fixed, q_rel, q_head, w.key_true, (unsigned)n_blocks, filter, N, w.removed);
         // the pair role: 64 pairs per wave and trip, four waves per workgroup, up to 10 workgroups per compute unit
         int64_t pair_blocks = (n_blocks * kSQuota + 255) / 256;
         pair_blocks = pair_blocks < (int64_t)n_cu * 10 ? pair_blocks : (int64_t)n_cu * 10;
@@ -758,6 +877,10 @@ static hipError_t rank_sad_impl(const float* table, int64_t N, int64_t ld, const
         }
     }
     if (ev_stop) (void)hipEventRecord(ev_stop, stream);
+    if (filter.on()) {  // the removed rows were scored by the first pre-pass launch's filter role
+        sad_finalize_kernel<<<(unsigned)((Q + 255) / 256), 256, 0, stream>>>(w.acc, w.removed, Q, counts);
+        return hipGetLastError();
+    }
     err = launch_filter_finalize(TRANSE, D, table, N, ld, q_fixed, q_rel, w.key_true, q_head, q_tail, filter,
                                  w.acc, counts, stream);
     return err != hipSuccess ? err : hipGetLastError();
