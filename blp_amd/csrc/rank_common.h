@@ -59,6 +59,14 @@ template <int BYTES>
 __device__ __forceinline__ void stouch(const float* row) {  // one dword per 64-B line, result discarded
     stouch_lines(row, std::make_integer_sequence<int, BYTES / 64>{});
 }
+template <int OFF, int... Ls>
+__device__ __forceinline__ void stouch_lines_from(const float* row, std::integer_sequence<int, Ls...>) {
+    (stouch_line<OFF + Ls * 64>(row), ...);
+}
+template <int OFF, int BYTES>
+__device__ __forceinline__ void stouch_from(const float* row) {  // the same, OFF bytes behind `row` (an immediate: no address arithmetic)
+    stouch_lines_from<OFF>(row, std::make_integer_sequence<int, BYTES / 64>{});
+}
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

@@ -253,6 +253,12 @@ constexpr unsigned kSadChunkBlock = BLP_SAD_CHUNK_BLOCK;  // query chunks whose 
 constexpr unsigned kSInlineCap = BLP_SAD_INLINE_CAP;
 static_assert(kSInlineCap <= kSQuota, "the pooled list is the four slices of pair_s");
 
+// Queries per trip of the pre-pass's query loop (rank_sad_kernel): 4, or 1 for the one-query loop alone.
+#ifndef BLP_SAD_TRIP
+#define BLP_SAD_TRIP 4
+#endif
+constexpr int kSadTrip = BLP_SAD_TRIP;
+
 // -DBLP_TIMING: per wave of the kernel below, shader-clock ticks and ticks of the constant 100 MHz counter, summed: their
 // ratio is the clock the kernel ran at (tools/gemm_ab.py --sad)
 #ifdef BLP_TIMING
@@ -350,7 +356,7 @@ __device__ __forceinline__ void sad_filter_role(unsigned vblock, unsigned vgrid,
 
 // Grid: n_prepass = n_groups x chunks pre-pass workgroups, then (first slab of a filtered call only) the filter role's.
 template <int D, int TPW>
-__global__ __launch_bounds__(kSW * 64, (TPW * D / 2 <= 64 ? 5 : TPW * D / 2 <= 128 ? 3 : 2)) void rank_sad_kernel(
+__global__ __launch_bounds__(kSW * 64, (TPW * D / 2 <= 64 ? (TPW == 1 ? 6 : 5) : TPW * D / 2 <= 128 ? 3 : 2)) void rank_sad_kernel(
     const uint4* __restrict__ cimg, const unsigned* __restrict__ resid, int64_t n_rows, int n_groups, int q_per_group,
     const unsigned* __restrict__ qimg, const int2* __restrict__ thr, int64_t Q, int words_per_query,
     unsigned long long* __restrict__ acc,
@@ -358,7 +364,7 @@ __global__ __launch_bounds__(kSW * 64, (TPW * D / 2 <= 64 ? 5 : TPW * D / 2 <= 1
     const float* __restrict__ table, int64_t ld, const QRows q_fixed, const QRows q_rel, int64_t q_head,
     const float* __restrict__ key_true, unsigned n_prepass, const FilterSpec filter, int64_t n_table,
     unsigned long long* __restrict__ removed) {
-    __shared__ int2 thr_s[kSChunk];
+    __shared__ __align__(16) int2 thr_s[kSChunk];  // (16: a trip's four entries are two 16-byte reads)
     __shared__ unsigned cnt[kSChunk];
     __shared__ uint2 pair_s[kSQuota];
     __shared__ unsigned wave_used[kSW], wave_base[kSW], ec_max_s;  // per-wave slices of pair_s: fill counts, global offsets
@@ -439,27 +445,30 @@ __global__ __launch_bounds__(kSW * 64, (TPW * D / 2 <= 64 ? 5 : TPW * D / 2 <= 1
     // query, ~70 scalar instructions per query (64-bit address arithmetic for three row pointers with end-of-block
     // clamps, the atomic optimiser's lane loop around the LDS count) kept the scalar pipe as busy as the SAD pipe and
     // the kernel at 78 % of the SAD rate.  So: pointers advance by a constant (the image is padded by four rows, no
-    // clamps), and a query's count goes to lane j % 64 of a register with one masked add; the register is flushed to
-    // the LDS counters once per 64 queries by all lanes.
+    // clamps), and the counts stay in ONE register for the whole chunk: query j's count is byte j % 4 of lane j / 4
+    // (a count is at most 64 x TPW, and a byte receives exactly one add: no carry crosses), flushed to the LDS counters
+    // once per workgroup and wave.  A trip of the loop takes kSadTrip consecutive queries one after another through the
+    // same SAD chain and the same double-buffered row pipeline; what the trip shares is the VALU work beside the chain:
+    // the four thresholds come from one LDS address (two 16-byte reads), the four counts are packed on the scalar side
+    // and go to the trip's lane with one masked add.  The nq % kSadTrip queries left over go one at a time.
+    static_assert(kSChunk <= 64 * 4 && 64 * TPW <= 255, "a chunk's counts: one byte per query, four queries per lane of cnt_reg");
+    static_assert(kSadTrip == 1 || kSadTrip == 4, "a trip is a lane of cnt_reg, or one query");
     unsigned my_pairs = 0;  // entries in this wave's slice of pair_s (wave-uniform)
     const float* row = reinterpret_cast<const float*>(qimg + q0 * (D / 2));
     sf16 cur = sload16<0>(row);
     sdrain(cur);
-    for (int jb = 0; jb < nq; jb += 64) {  // 64 queries per flush of the count register
-    const int jn = nq - jb < 64 ? nq - jb : 64;
-    unsigned cnt_reg = 0;  // lane l: certainly-above count of query jb + l
-    unsigned long long bit = 1;
-    for (int j = jb; j < jb + jn; ++j, row += D / 2, bit <<= 1) {
-        const float* next_row = row + D / 2;  // rows past the block's last query: the next block's, or the padding
-        const int2 th = thr_s[j];
+    unsigned cnt_reg = 0;  // lane l, byte b: certainly-above count of query 4 l + b
+    // Query j, whose row is S rows behind `row` (rows past the block's last query: the next block's, or the padding);
+    // `touch`: the four waves walk the same rows and take turns touching the lines of the query three ahead.
+    auto one_query = [&](auto ss, const int j, const int2 th, const bool touch) -> unsigned {
+        constexpr int S = decltype(ss)::value;
         unsigned sad[TPW];
         static_for<TPW>([&](auto tt) { sad[decltype(tt)::value] = c.bias[decltype(tt)::value]; });
         static_for<D / 32>([&](auto kk) {
             constexpr int k = decltype(kk)::value;
             sf16 nxt;
-            if constexpr (k + 1 < D / 32) nxt = sload16<(k + 1) * 64>(row); else nxt = sload16<0>(next_row);
-            // the four waves walk the same rows: they take turns touching the lines of the query three ahead
-            if constexpr (k == 0) { if ((j & 3) == wave) stouch<D * 2>(row + 3 * (D / 2)); }
+            if constexpr (k + 1 < D / 32) nxt = sload16<S * D * 2 + (k + 1) * 64>(row); else nxt = sload16<(S + 1) * D * 2>(row);
+            if constexpr (k == 0) { if (touch) stouch_from<(S + 3) * D * 2, D * 2>(row); }
             static_for<16>([&](auto ii) {
                 constexpr int i = decltype(ii)::value;
                 const float qf = cur[i];  // (bit_cast straight from the vector element reads element 0)
@@ -481,8 +490,11 @@ __global__ __launch_bounds__(kSW * 64, (TPW * D / 2 <= 64 ? 5 : TPW * D / 2 <= 1
             if (und) {  // wave-uniform.  The wave fills its own slice of the list: no LDS round trip for a slot
                 const unsigned n = __popcll(und);
                 if (my_pairs + n <= kSQuota / kSW) {
-                    if ((und >> lane) & 1ull)
-                        pair_s[wave * (kSQuota / kSW) + my_pairs + __popcll(und & ((1ull << lane) - 1ull))] =
+                    // (the lane's bit and the bits below it straight from the scalar mask: no per-lane masks held in
+                    // registers across the loop for this rare branch)
+                    if (__builtin_amdgcn_inverse_ballot_w64(und))
+                        pair_s[wave * (kSQuota / kSW) + my_pairs +
+                               __builtin_amdgcn_mbcnt_hi((unsigned)(und >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)und, 0u))] =
                             make_uint2((unsigned)(q0 + j), (unsigned)((tile0 + t) * 64 + lane));
                     my_pairs += n;
                 } else {
@@ -493,14 +505,38 @@ __global__ __launch_bounds__(kSW * 64, (TPW * D / 2 <= 64 ? 5 : TPW * D / 2 <= 1
             }
             n_above += n_t;
         });
-        {   // cnt_reg[lane j - jb] += n_above: one VALU instruction under a one-lane exec mask
-            unsigned long long saved;
-            asm volatile("s_mov_b64 %1, exec\n\ts_mov_b64 exec, %3\n\tv_add_u32 %0, %0, %2\n\ts_mov_b64 exec, %1"
-                         : "+v"(cnt_reg), "=&s"(saved) : "s"(n_above), "s"(bit));
+        return n_above;
+    };
+    // cnt_reg[lane of `bit`] += packed: one VALU instruction under a one-lane exec mask
+    auto add_counts = [&](const unsigned packed, const unsigned long long bit) {
+        unsigned long long saved;
+        asm volatile("s_mov_b64 %1, exec\n\ts_mov_b64 exec, %3\n\tv_add_u32 %0, %0, %2\n\ts_mov_b64 exec, %1"
+                     : "+v"(cnt_reg), "=&s"(saved) : "s"(packed), "s"(bit));
+    };
+    int j = 0;
+    if constexpr (kSadTrip == 4) {
+        for (; j + 4 <= nq; j += 4, row += 4 * (D / 2)) {
+            const int4* th4 = reinterpret_cast<const int4*>(thr_s + j);  // (x: T_lo, y: T_hi) of the trip's four queries
+            const int4 ta = th4[0];
+            int turn = wave;  // (opaque: compared where it is used, not kept as four lane masks across the loop)
+            asm volatile("" : "+s"(turn));
+            unsigned packed = one_query(std::integral_constant<int, 0>{}, j, make_int2(ta.x, ta.y), turn == 0);
+            packed |= one_query(std::integral_constant<int, 1>{}, j + 1, make_int2(ta.z, ta.w), turn == 1) << 8;
+            const int4 tb = th4[1];  // the same address register, 16 bytes on: in flight under the third query's SADs
+            packed |= one_query(std::integral_constant<int, 2>{}, j + 2, make_int2(tb.x, tb.y), turn == 2) << 16;
+            packed |= one_query(std::integral_constant<int, 3>{}, j + 3, make_int2(tb.z, tb.w), turn == 3) << 24;
+            add_counts(packed, 1ull << (j >> 2));
         }
     }
-    if (cnt_reg) atomicAdd(&cnt[jb + lane], cnt_reg);  // all lanes: distinct counters, plain ds_add_u32
-    }
+    // one query at a time: the chunk's last nq % 4 (thr_s and the rows behind them hold padding that would read as
+    // undecided: those are never walked), or every query where the trip is off
+    for (; j < nq; ++j, row += D / 2)
+        add_counts(one_query(std::integral_constant<int, 0>{}, j, thr_s[j], (j & 3) == wave) << 8 * (j & 3), 1ull << (j >> 2));
+    static_for<4>([&](auto bb) {  // all lanes: distinct counters, plain ds_add_u32; most bytes of a short chunk are zero
+        constexpr int b = decltype(bb)::value;
+        const unsigned n = cnt_reg >> 8 * b & 255u;
+        if (n) atomicAdd(&cnt[4 * lane + b], n);
+    });
     __syncthreads();
     for (int i = tid; i < nq; i += kSW * 64) {
         const unsigned long long v = cnt[i];
