@@ -31,6 +31,7 @@ SYMBOLS = ("blp_version", "blp_last_error", "blp_device_caps", "blp_selftest", "
            "blp_topk_typed_supported", "blp_topk_typed_workspace_bytes", "blp_topk_typed",
            "blp_topk_wide_supported", "blp_topk_wide_workspace_bytes", "blp_topk_wide",
            "blp_rank_lists_supported", "blp_rank_lists_workspace_bytes", "blp_rank_lists",
+           "blp_rank_lists_wide_supported", "blp_rank_lists_wide_workspace_bytes", "blp_rank_lists_wide",
            "blp_rank_sets_supported", "blp_rank_sets_workspace_bytes", "blp_rank_sets",
            "blp_rank_sets_typed_supported", "blp_rank_sets_typed_workspace_bytes", "blp_rank_sets_typed",
            "blp_rank_sets_wide_supported", "blp_rank_sets_wide_workspace_bytes", "blp_rank_sets_wide",
@@ -239,6 +240,10 @@ def _load(path, hooks):
     L.blp_rank_lists.restype = _i
     L.blp_rank_lists.argtypes = [_i, _vp, _i, _i64, _i, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp,
                                  _i64, ctypes.POINTER(BlpFilter), _vp, _vp, _vp, _sz, _i, _vp]
+    for wide, lists in ((L.blp_rank_lists_wide_supported, L.blp_rank_lists_supported),
+                        (L.blp_rank_lists_wide_workspace_bytes, L.blp_rank_lists_workspace_bytes),
+                        (L.blp_rank_lists_wide, L.blp_rank_lists)):  # blp_rank_lists' signatures, by design
+        wide.restype, wide.argtypes = lists.restype, list(lists.argtypes)
     L.blp_rank_sets_supported.restype = _i
     L.blp_rank_sets_supported.argtypes = [_i, _i]
     L.blp_rank_sets_workspace_bytes.restype = _sz

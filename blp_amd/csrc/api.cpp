@@ -822,15 +822,18 @@ size_t blp_rank_lists_workspace_bytes(int model, int table_dtype, int D, int64_t
     return blp::rank_lists_workspace_bytes(q_head, q_tail);
 }
 
-int blp_rank_lists(int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld, int64_t row_base, const float* source,
-                   int64_t S, int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R, const int64_t* rel_id,
-                   const int64_t* true_row, int64_t q_head, int64_t q_tail, const int64_t* list_ptr, const int64_t* list_row,
-                   int64_t nnz, const blp_filter* filter, int32_t* counts, float* scores, void* workspace, size_t workspace_bytes,
-                   int device, void* stream) {
-    const char* who = "blp_rank_lists";
+// blp_rank_lists and blp_rank_lists_wide: one argument list, one sequence of checks; `wide` picks the limits and the launcher
+static int rank_lists_call(const char* who, bool wide, int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld,
+                           int64_t row_base, const float* source, int64_t S, int64_t ld_src, const int64_t* fixed_row,
+                           const float* rel_emb, int64_t R, const int64_t* rel_id, const int64_t* true_row, int64_t q_head,
+                           int64_t q_tail, const int64_t* list_ptr, const int64_t* list_row, int64_t nnz, const blp_filter* filter,
+                           int32_t* counts, float* scores, void* workspace, size_t workspace_bytes, int device, void* stream) {
     if (!valid_model(model)) return fail(BLP_ERR_BAD_ARG, "%s: unknown model %d", who, model);
     if (!valid_table_dtype(table_dtype)) return fail(BLP_ERR_BAD_ARG, "%s: unknown table dtype %d", who, table_dtype);
-    if (!blp_rank_lists_supported(model, table_dtype, D))
+    if (wide && !blp::rank_lists_wide_supported(model, table_dtype, D))
+        return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: model %d at D = %d not supported (DistMult / ComplEx / SimplE at D %% 4 == 0 from 4 up "
+                                             "to 1024: see blp_rank_lists_wide_supported; TransE: blp_rank_lists)", who, model, D);
+    if (!wide && !blp_rank_lists_supported(model, table_dtype, D))
         return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (TransE: D %% 4 == 0 up to 1024; the other models: 64 / 128 / "
                                              "256: see blp_rank_lists_supported)", who, D);
     if (N < 0 || q_head < 0 || q_tail < 0 || ld < D || row_base < 0 || nnz < 0)
@@ -866,17 +869,48 @@ int blp_rank_lists(int model, const void* table, int table_dtype, int64_t N, int
         spec.row_base = filter->row_base;
     }
     if (Q == 0) return BLP_OK;
-    const size_t need = counts ? blp::rank_lists_workspace_bytes(q_head, q_tail) : 0;
+    const size_t need = !counts ? 0 : (wide ? blp::rank_lists_wide_workspace_bytes(q_head, q_tail) : blp::rank_lists_workspace_bytes(q_head, q_tail));
     if (need && (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255u)))
         return fail(BLP_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned and >= %zu bytes (got %zu)", who, need, workspace_bytes);
     DeviceGuard guard(device);
     if (guard.error() != hipSuccess) return hip_fail(guard.error(), "hipSetDevice");
     const blp::QRows truth = true_row ? blp::QRows::rows_of(source, true_row, ld_src) : blp::QRows();
-    hipError_t err = blp::launch_rank_lists(model, D, table_dtype, table, N, ld, row_base, blp::QRows::rows_of(source, fixed_row, ld_src),
-                                            blp::QRows::rows_of(rel_emb, rel_id, D), truth, q_head, q_tail, list_ptr, list_row, nnz, spec,
-                                            counts, scores, workspace, static_cast<hipStream_t>(stream));
-    if (err != hipSuccess) return hip_fail(err, "blp_rank_lists launch");
+    const auto launch = wide ? blp::launch_rank_lists_wide : blp::launch_rank_lists;
+    hipError_t err = launch(model, D, table_dtype, table, N, ld, row_base, blp::QRows::rows_of(source, fixed_row, ld_src),
+                            blp::QRows::rows_of(rel_emb, rel_id, D), truth, q_head, q_tail, list_ptr, list_row, nnz, spec, counts, scores,
+                            workspace, static_cast<hipStream_t>(stream));
+    if (err != hipSuccess) return hip_fail(err, wide ? "blp_rank_lists_wide launch" : "blp_rank_lists launch");
     return BLP_OK;
+}
+
+int blp_rank_lists(int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld, int64_t row_base, const float* source,
+                   int64_t S, int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R, const int64_t* rel_id,
+                   const int64_t* true_row, int64_t q_head, int64_t q_tail, const int64_t* list_ptr, const int64_t* list_row,
+                   int64_t nnz, const blp_filter* filter, int32_t* counts, float* scores, void* workspace, size_t workspace_bytes,
+                   int device, void* stream) {
+    return rank_lists_call("blp_rank_lists", false, model, table, table_dtype, N, D, ld, row_base, source, S, ld_src, fixed_row, rel_emb,
+                           R, rel_id, true_row, q_head, q_tail, list_ptr, list_row, nnz, filter, counts, scores, workspace,
+                           workspace_bytes, device, stream);
+}
+
+// ---- per-query candidate lists, DistMult / ComplEx / SimplE at any width (rank_lists_wide.hip)
+int blp_rank_lists_wide_supported(int model, int table_dtype, int D) {
+    return valid_model(model) && blp::rank_lists_wide_supported(model, table_dtype, D) ? 1 : 0;
+}
+
+size_t blp_rank_lists_wide_workspace_bytes(int model, int table_dtype, int D, int64_t q_head, int64_t q_tail) {
+    if (!blp_rank_lists_wide_supported(model, table_dtype, D) || q_head < 0 || q_tail < 0) return 0;
+    return blp::rank_lists_wide_workspace_bytes(q_head, q_tail);
+}
+
+int blp_rank_lists_wide(int model, const void* table, int table_dtype, int64_t N, int D, int64_t ld, int64_t row_base,
+                        const float* source, int64_t S, int64_t ld_src, const int64_t* fixed_row, const float* rel_emb, int64_t R,
+                        const int64_t* rel_id, const int64_t* true_row, int64_t q_head, int64_t q_tail, const int64_t* list_ptr,
+                        const int64_t* list_row, int64_t nnz, const blp_filter* filter, int32_t* counts, float* scores,
+                        void* workspace, size_t workspace_bytes, int device, void* stream) {
+    return rank_lists_call("blp_rank_lists_wide", true, model, table, table_dtype, N, D, ld, row_base, source, S, ld_src, fixed_row,
+                           rel_emb, R, rel_id, true_row, q_head, q_tail, list_ptr, list_row, nnz, filter, counts, scores, workspace,
+                           workspace_bytes, device, stream);
 }
 
 // ---- filtered top-k inside per-query candidate lists (lists_topk.hip)

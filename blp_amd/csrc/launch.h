@@ -142,6 +142,15 @@ hipError_t launch_rank_lists(int model, int D, int dtype, const void* table, int
                              const int64_t* list_ptr, const int64_t* list_row, int64_t nnz, const FilterSpec& filter, int32_t* counts,
                              float* scores, void* workspace, hipStream_t stream);
 
+// rank_lists_wide.hip: the same contract for DistMult / ComplEx / SimplE at any D % 4 == 0, 4 <= D <= 1024 (include/blp_hip.h:
+// blp_rank_lists_wide), by wide_bilinear.h's arithmetic; launch_rank_lists' argument list.
+bool rank_lists_wide_supported(int model, int dtype, int D);
+size_t rank_lists_wide_workspace_bytes(int64_t q_head, int64_t q_tail);
+hipError_t launch_rank_lists_wide(int model, int D, int dtype, const void* table, int64_t N, int64_t ld, int64_t row_base,
+                                  const QRows q_fixed, const QRows q_rel, const QRows q_true, int64_t q_head, int64_t q_tail,
+                                  const int64_t* list_ptr, const int64_t* list_row, int64_t nnz, const FilterSpec& filter,
+                                  int32_t* counts, float* scores, void* workspace, hipStream_t stream);
+
 // lists_topk.hip: filtered top-k inside per-query candidate lists (include/blp_hip.h: blp_topk_lists): rank_lists' queries,
 // table and lists, topk's output.  The workspace holds the (Q, S, k) partial key lists when a query's list is cut into S > 1
 // slabs (S from Q and nnz alone), else nothing.

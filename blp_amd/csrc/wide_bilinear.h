@@ -24,6 +24,7 @@
 
 #include "rank_common.h"
 #include "score_core.h"
+#include "table_elem.h"
 
 #pragma clang fp contract(off)
 
@@ -356,6 +357,134 @@ __device__ __forceinline__ float wide_pair_score(const float* __restrict__ e, co
     }
     float s = 0.0f;
     for (int j = 8 * vec_size; j < n; ++j) s = s + term_at(j);
+    return wide_fold<MODEL>(acc, s);
+}
+
+// ---- one candidate row against ONE query whose coefficients are staged (rank_lists_wide.hip): wide_trip at one query and
+// one row, templated on the table's element type (table_elem.h: a 16-bit element is widened exactly as it is read).
+
+// A wave stages one query's coefficients: coef[K][n4] as wide_stage_coef lays them out, zero beyond n.  The caller puts the
+// wave_lds_sync()s around it.
+template <int MODEL, int SIDE>
+__device__ __forceinline__ void wide_stage_coef_wave(float* coef, const float* __restrict__ f, const float* __restrict__ r, int D,
+                                                     int lane) {
+    using T = WideTerm<MODEL, SIDE>;
+    const int H = D / 2, n = MODEL == DISTMULT ? D : H, n4 = (n + 3) & ~3;
+#pragma unroll
+    for (int k = 0; k < T::K; ++k)
+        for (int j = lane; j < n4; j += 64) coef[k * n4 + j] = j < n ? T::coef(f, r, j, H, k) : 0.0f;
+}
+
+// one element, and four consecutive elements at an address aligned to two of them (the second half of a row: H is even,
+// not always a multiple of 4), widened
+template <class TE>
+__device__ __forceinline__ float wide_elem(const TE* p);
+template <>
+__device__ __forceinline__ float wide_elem<float>(const float* p) { return *p; }
+template <>
+__device__ __forceinline__ float wide_elem<_Float16>(const _Float16* p) { return (float)*p; }
+template <>
+__device__ __forceinline__ float wide_elem<__bf16>(const __bf16* p) {
+    return __builtin_bit_cast(float, (unsigned)*reinterpret_cast<const unsigned short*>(p) << 16);
+}
+
+template <class TE>
+__device__ __forceinline__ float4 wide_load4_halves(const TE* p) {
+    const unsigned lo = *reinterpret_cast<const unsigned*>(p), hi = *reinterpret_cast<const unsigned*>(p + 2);
+    float4 v;
+    widen_pair<TE>(lo, v.x, v.y);
+    widen_pair<TE>(hi, v.z, v.w);
+    return v;
+}
+template <>
+__device__ __forceinline__ float4 wide_load4_halves<float>(const float* p) {
+    const float2 lo = *reinterpret_cast<const float2*>(p), hi = *reinterpret_cast<const float2*>(p + 2);
+    return make_float4(lo.x, lo.y, hi.x, hi.y);
+}
+
+// four columns of one candidate row
+struct WidePairCols {
+    float4 a, b;
+};
+
+template <bool HALVES, class TE>
+__device__ __forceinline__ WidePairCols wide_pair_load(const TE* p, int col, int H) {
+    WidePairCols e;
+    e.a = load4<TE>(p + col);
+    e.b = HALVES ? wide_load4_halves<TE>(p + H + col) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // (else never used)
+    return e;
+}
+
+// acc[c] += term of column col + c (col: the lane's first of four): one 16-byte coefficient read per array
+template <int MODEL, int SIDE>
+__device__ __forceinline__ void wide_pair_step(float (&acc)[4], const WidePairCols& e, const float* coef, int n4, int col) {
+    using T = WideTerm<MODEL, SIDE>;
+    float c4[T::K][4];
+#pragma unroll
+    for (int k = 0; k < T::K; ++k) {
+        const float4 v = *reinterpret_cast<const float4*>(coef + k * n4 + col);
+        c4[k][0] = v.x; c4[k][1] = v.y; c4[k][2] = v.z; c4[k][3] = v.w;
+    }
+    const float ea[4] = {e.a.x, e.a.y, e.a.z, e.a.w}, eb[4] = {e.b.x, e.b.y, e.b.z, e.b.w};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        float ck[T::K];
+#pragma unroll
+        for (int k = 0; k < T::K; ++k) ck[k] = c4[k][c];
+        acc[c] = acc[c] + T::term(ea[c], eb[c], ck);
+    }
+}
+
+// The score of candidate row e (its first element) against the query whose coefficients wide_stage_coef_wave put in `coef`:
+// wide_trip's order at one query and one row -- the next 32-term row's load in flight behind the current row's arithmetic,
+// the cascade after rows 16 and 32 (CASCADE == (n >= 512)), the leftover vectors in lanes 0 and 1, the tail terms first, the
+// fold.  Every lane of the wave must call; the result is valid in lanes 0 .. 3 of the eight.
+template <int MODEL, int SIDE, bool CASCADE, class TE>
+__device__ __forceinline__ float wide_pair_staged(const TE* __restrict__ e, const float* coef, int D, int sub) {
+    using T = WideTerm<MODEL, SIDE>;
+    constexpr int K = T::K;
+    const int H = D / 2, n = MODEL == DISTMULT ? D : H, n4 = (n + 3) & ~3;
+    const int size_ilp = n / 32, vec_size = n / 8, n_left = vec_size - 4 * size_ilp;
+    const TE* p = e + 4 * sub;  // the row at the lane's four columns
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    float up[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    WidePairCols cur;
+    if (size_ilp > 0) cur = wide_pair_load<T::kHalves, TE>(p, 0, H);
+#pragma unroll 1
+    for (int i = 0; i < size_ilp; ++i) {
+        const WidePairCols nxt = wide_pair_load<T::kHalves, TE>(p, i + 1 < size_ilp ? 32 * (i + 1) : 32 * i, H);
+        wide_pair_step<MODEL, SIDE>(acc, cur, coef, n4, 32 * i + 4 * sub);
+        cur = nxt;
+        if constexpr (CASCADE) {
+            if (((i + 1) & 15) == 0) {  // after rows 16 and 32: one level up
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    up[c] = up[c] + acc[c];
+                    acc[c] = 0.0f;
+                }
+            }
+        }
+    }
+    if constexpr (CASCADE) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[c] = acc[c] + up[c];
+    }
+    // the leftover vectors of 8: accumulators 0 .. 7, i.e. lanes 0 and 1 of the group
+    for (int v = 0; v < n_left; ++v) {
+        if (sub < 2) {
+            const int col = 32 * size_ilp + 8 * v;
+            const WidePairCols x = wide_pair_load<T::kHalves, TE>(p, col, H);
+            wide_pair_step<MODEL, SIDE>(acc, x, coef, n4, col + 4 * sub);
+        }
+    }
+    // the n % 8 tail terms, one after the other (every lane of the group the same)
+    float s = 0.0f;
+    for (int j = 8 * vec_size; j < n; ++j) {
+        float ck[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) ck[k] = coef[k * n4 + j];
+        s = s + T::term(wide_elem<TE>(e + j), T::kHalves ? wide_elem<TE>(e + H + j) : 0.0f, ck);
+    }
     return wide_fold<MODEL>(acc, s);
 }
 

@@ -5,6 +5,7 @@ device memory and the stream; every arithmetic step of the hot path runs in the 
     rank_metrics(...)   counts -> reciprocal ranks, hits   (utils.py:104-109)
     topk(...)           filtered top-k prediction per query (no score matrix)
     rank_lists(...)     counts / scores of per-query candidate lists (only the listed rows are read)
+    rank_lists_wide(...) the same for DistMult / ComplEx / SimplE at any width D % 4 == 0, 4 <= D <= 1024
     rank_sets(...)      counts against candidate sets shared by groups of queries (type-constrained evaluation)
     rank_sets_wide(...) the same for TransE at any width D % 4 == 0, 4 <= D <= 1024 (the BOW / DKRL 300 and 768)
     rank_sets_wide_bilinear(...) the same for DistMult / ComplEx / SimplE at those widths, a float32 table
@@ -502,6 +503,32 @@ def rank_lists(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, li
     score (a multiset: duplicates count; ``filter``: a SegmentFilter whose row_base is ``row_base``).  ``want_scores`` (or no
     true_row): scores (nnz,) float32, score_fn's values bit for bit.  Returns (counts or None, scores or None); ``out`` may
     give both (None for the one not wanted)."""
+    return _rank_lists(False, rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, list_ptr, list_row, true_row, filter,
+                       row_base, want_scores, out)
+
+
+def rank_lists_wide_supported(rel_model, dim, dtype=torch.float32):
+    """True if rank_lists_wide takes this model, width and table dtype (blp_rank_lists_wide_supported: distmult, complex or
+    simple, D % 4 == 0, 4 <= D <= 1024 -- the BOW / DKRL encoders' 300 and 768; a float32, float16 or bfloat16 table)."""
+    if dtype not in TABLE_DTYPES:
+        return False
+    return bool(_lib.lib().blp_rank_lists_wide_supported(_lib.MODEL_IDS[rel_model], TABLE_DTYPES[dtype], int(dim)))
+
+
+def rank_lists_wide(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, list_ptr, list_row, true_row=None, filter=None,
+                    row_base=0, want_scores=False, out=None):
+    """rank_lists for DistMult / ComplEx / SimplE at any width D % 4 == 0, 4 <= D <= 1024 (blp_rank_lists_wide: eight lanes per
+    (entry, query) pair in rank_all_wide's sum order, the query's coefficients staged per wave in LDS): same arguments, same
+    counts and scores -- the reference's bit for bit, on a 16-bit table those of the table widened to float32.  At 64 / 128 /
+    256 it gives rank_lists' bits by a second implementation."""
+    return _rank_lists(True, rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, list_ptr, list_row, true_row, filter,
+                       row_base, want_scores, out)
+
+
+def _rank_lists(wide, rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, list_ptr, list_row, true_row, filter, row_base,
+                want_scores, out):
+    """rank_lists (blp_rank_lists) and rank_lists_wide (blp_rank_lists_wide): one argument handling, two entries."""
+    who = "rank_lists_wide" if wide else "rank_lists"
     _require_device(table, source, fixed_row, rel_emb, rel_ids, list_ptr, list_row, true_row)
     if source is table and table.dtype != torch.float32:
         raise TypeError("a 16-bit table needs a float32 `source` for the queries' vectors")
@@ -518,10 +545,13 @@ def rank_lists(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, li
         raise ValueError("fixed_row and rel_ids need one entry per query, list_ptr Q + 1; rel_emb must be (R, D)")
     if not 0 <= q_head <= Q:
         raise ValueError(f"q_head = {q_head} outside [0, {Q}]")
-    if not rank_lists_supported(rel_model, D, table.dtype):
+    if wide and not rank_lists_wide_supported(rel_model, D, table.dtype):
+        raise ValueError(f"rank_lists_wide: {rel_model} at D = {D} not supported (distmult / complex / simple, D % 4 == 0, "
+                         "4 <= D <= 1024: see rank_lists_wide_supported)")
+    if not wide and not rank_lists_supported(rel_model, D, table.dtype):
         raise ValueError(f"rank_lists: D = {D} not supported for {rel_model} (see rank_lists_supported)")
     if filter is not None and int(filter.row_base) != int(row_base):
-        raise ValueError(f"rank_lists: the filter's row_base {filter.row_base} differs from row_base {row_base}")
+        raise ValueError(f"{who}: the filter's row_base {filter.row_base} differs from row_base {row_base}")
     want_scores = bool(want_scores) or true_row is None
     dev = table.device
     counts, scores = out if out is not None else (None, None)
@@ -548,16 +578,17 @@ def rank_lists(rel_model, table, source, fixed_row, rel_emb, rel_ids, q_head, li
     model = _lib.MODEL_IDS[rel_model]
     tdt = TABLE_DTYPES[table.dtype]
     stream = torch._C._cuda_getCurrentRawStream(dev.index)
-    ws_bytes = L.blp_rank_lists_workspace_bytes(model, tdt, D, q_head, Q - q_head) if counts is not None else 0
+    entry = "blp_rank_lists_wide" if wide else "blp_rank_lists"
+    ws_bytes = getattr(L, entry + "_workspace_bytes")(model, tdt, D, q_head, Q - q_head) if counts is not None else 0
     workspace = _workspace(dev, stream, ws_bytes) if ws_bytes else None
     spec = None if filter is None else _filter_spec(filter, Q, dev)
-    status = L.blp_rank_lists(model, table.data_ptr(), tdt, N, D, table.stride(0) if tdt or N > 1 else D, int(row_base),
-                              source.data_ptr(), source.shape[0], source.stride(0) if source.shape[0] > 1 else D, fixed_row.data_ptr(),
-                              rel_emb.data_ptr(), rel_emb.shape[0], rel_ids.data_ptr(), _addr(true_row), q_head, Q - q_head,
-                              list_ptr.data_ptr(), list_row.data_ptr(), nnz, spec, _addr(counts), _addr(scores), _addr(workspace),
-                              ws_bytes, dev.index, stream)
+    status = getattr(L, entry)(model, table.data_ptr(), tdt, N, D, table.stride(0) if tdt or N > 1 else D, int(row_base),
+                               source.data_ptr(), source.shape[0], source.stride(0) if source.shape[0] > 1 else D, fixed_row.data_ptr(),
+                               rel_emb.data_ptr(), rel_emb.shape[0], rel_ids.data_ptr(), _addr(true_row), q_head, Q - q_head,
+                               list_ptr.data_ptr(), list_row.data_ptr(), nnz, spec, _addr(counts), _addr(scores), _addr(workspace),
+                               ws_bytes, dev.index, stream)
     if status:
-        _lib.check(status, "blp_rank_lists")
+        _lib.check(status, entry)
     return counts, scores
 
 

@@ -670,8 +670,8 @@ def sample_candidates(num_queries, num_rows, c, generator=None, device=None):
 def _rank_lists_dense(score_fn, table, fixed, rel, true_vec, q_head, ptr, rows, row_base, filt, want_scores,
                       max_bytes=1 << 28):
     """The dense route of rank_candidates: score_fn on the gathered rows of the lists, in query chunks of bounded bytes, the
-    comparisons against the true score, the filter through _filtered_pairs.  CPU tensors and widths blp_rank_lists does not
-    take; on CPU tensors it is the oracle of the fused route.  fixed / rel / true_vec: (Q, D) float32 (true_vec None: scores
+    comparisons against the true score, the filter through _filtered_pairs.  CPU tensors and the widths neither blp_rank_lists
+    nor blp_rank_lists_wide takes; on CPU tensors it is the oracle of the fused routes.  fixed / rel / true_vec: (Q, D) float32 (true_vec None: scores
     only); ptr (Q + 1,), rows (nnz,) global rows.  Returns (counts (Q, 4) int32 or None, scores (nnz,) or None)."""
     Q, (N, D) = fixed.shape[0], table.shape
     dev = table.device
@@ -730,8 +730,10 @@ def rank_candidates(model, table, triples, candidates, ent2idx, *, side="both", 
                  rank_all's mean (the true entity ties with itself) and metrics_from_counts applies unchanged
     Returns counts (Q, 4) int32 {gt, ge, gt_filtered, ge_filtered}; with return_scores also the candidates' scores in the
     caller's layout ((Q, C), or (nnz,); NaN at padding and skipped entries), score_fn's values bit for bit.
-    A HIP table at a width blp_rank_lists takes goes through it (a float16 / bfloat16 table is read as it is; only the Q fixed
-    and true rows are widened); CPU tensors and other widths take the dense route: score_fn on gathered rows."""
+    A HIP table at a width blp_rank_lists takes goes through it, a DistMult / ComplEx / SimplE model at any other width
+    D % 4 == 0, 4 <= D <= 1024 (the BOW / DKRL encoders' 300 and 768) through blp_rank_lists_wide (a float16 / bfloat16 table
+    is read as it is; only the Q fixed and true rows are widened); CPU tensors and everything else take the dense route:
+    score_fn on gathered rows."""
     model = _module(model)
     if side not in ("head", "tail", "both"):
         raise ValueError(f"side must be 'head', 'tail' or 'both', got {side!r}")
@@ -778,14 +780,19 @@ def rank_candidates(model, table, triples, candidates, ent2idx, *, side="both", 
         sel = torch.cat([x for x, on in ((torch.arange(T, device=device), heads), (torch.arange(T, 2 * T, device=device), tails)) if on])
         filt = ops.SegmentFilter(seg.seg_lo[sel].contiguous(), seg.seg_hi[sel].contiguous(), seg.values,
                                  seg.exclude[sel].contiguous(), seg.ent2idx, 0)
+    fused = None
     if table.is_cuda and ops.rank_lists_supported(model.rel_model, D, table.dtype):
+        fused = ops.rank_lists
+    elif table.is_cuda and ops.rank_lists_wide_supported(model.rel_model, D, table.dtype):
+        fused = ops.rank_lists_wide  # DistMult / ComplEx / SimplE off 64 / 128 / 256: the BOW / DKRL widths
+    if fused is not None:
         if table.dtype != torch.float32:  # float32 query vectors: the Q fixed and the Q true rows, widened (exact)
             source = table[torch.cat((fixed_rows, true_rows))].float()
             src_fixed, src_true = torch.arange(Q, device=device), torch.arange(Q, 2 * Q, device=device)
         else:
             source, src_fixed, src_true = table, fixed_rows, true_rows
-        counts, scores = ops.rank_lists(model.rel_model, table, source, src_fixed, rel_w, rel_ids, q_head, ptr, rows,
-                                        true_row=src_true, filter=filt, want_scores=return_scores)
+        counts, scores = fused(model.rel_model, table, source, src_fixed, rel_w, rel_ids, q_head, ptr, rows,
+                               true_row=src_true, filter=filt, want_scores=return_scores)
     else:
         dense_filt = None if filt is None else (filt.seg_lo, filt.seg_hi, filt.values, filt.exclude, filt.ent2idx)
         counts, scores = _rank_lists_dense(model.score_fn, table, table[fixed_rows].float(), rel_w[rel_ids],

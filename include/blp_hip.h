@@ -589,6 +589,29 @@ int blp_rank_lists(int model, const void *table, int table_dtype, int64_t N, int
                    const int64_t *list_row, int64_t nnz, const blp_filter *filter, int32_t *counts, float *scores,
                    void *workspace, size_t workspace_bytes, int device, void *stream);
 
+/* Per-query candidate lists for DistMult / ComplEx / SimplE at ANY width (the BOW / DKRL encoders' 300 and 768).  The
+ * contract is blp_rank_lists' word for word -- queries, table (f32 / f16 / bf16, widened exactly), row_base shards, the lists
+ * CSR, skipped entries (score slot 0x7fc00000), counts and / or scores (score_fn's value bit for bit, sign of zero included),
+ * the filter, the argument checks with their status codes, deterministic whatever the grid, asynchronous on `stream`, no
+ * allocation -- and so is the argument list.
+ * Limits (blp_rank_lists_wide_supported): model DistMult / ComplEx / SimplE (TransE: BLP_ERR_UNSUPPORTED_DIM -- blp_rank_lists
+ * takes it at these widths); table_dtype BLP_DTYPE_F32 / F16 / BF16; D % 4 == 0, 4 <= D <= 1024; everything else 0.  The
+ * other limits (nnz, rows, Q, alignment) are blp_rank_lists'.
+ * At D in {64, 128, 256} it is a second implementation of blp_rank_lists' bits; blp_rank_lists is the call
+ * ranking.rank_candidates routes there.
+ * One code object per (model, table dtype) for every width: eight lanes per (entry, query) pair sum in the reference's order,
+ * the query's coefficients staged once per (wave, query) in LDS.
+ * Workspace: blp_rank_lists_wide_workspace_bytes(...) bytes, 256-B aligned, needed with counts only: 4 Q bytes rounded up to
+ * 256 (the true keys) -- independent of N, D and nnz; 0 where unsupported and for a negative size.
+ * (Added after 6.0.0 without a version change: no existing entry point changed.) */
+int blp_rank_lists_wide_supported(int model, int table_dtype, int D);
+size_t blp_rank_lists_wide_workspace_bytes(int model, int table_dtype, int D, int64_t q_head, int64_t q_tail);
+int blp_rank_lists_wide(int model, const void *table, int table_dtype, int64_t N, int D, int64_t ld, int64_t row_base,
+                        const float *source, int64_t S, int64_t ld_src, const int64_t *fixed_row, const float *rel_emb, int64_t R,
+                        const int64_t *rel_id, const int64_t *true_row, int64_t q_head, int64_t q_tail, const int64_t *list_ptr,
+                        const int64_t *list_row, int64_t nnz, const blp_filter *filter, int32_t *counts, float *scores,
+                        void *workspace, size_t workspace_bytes, int device, void *stream);
+
 /* --------------------------------------------------------------------------------------------
  * Candidate sets SHARED between queries: rank a query against the rows of a set that a whole group of queries ranks against --
  * type-constrained evaluation (a head query of relation r against the entities seen as heads of r, a tail query against
