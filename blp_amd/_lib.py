@@ -44,6 +44,9 @@ SYMBOLS = ("blp_version", "blp_last_error", "blp_device_caps", "blp_selftest", "
            "blp_topk_relations_supported", "blp_topk_relations_workspace_bytes", "blp_topk_relations",
            "blp_rank_relations_wide_supported", "blp_rank_relations_wide_workspace_bytes", "blp_rank_relations_wide",
            "blp_topk_relations_wide_supported", "blp_topk_relations_wide_workspace_bytes", "blp_topk_relations_wide",
+           "blp_rank_relations_wide_bilinear_supported", "blp_rank_relations_wide_bilinear_workspace_bytes",
+           "blp_rank_relations_wide_bilinear", "blp_topk_relations_wide_bilinear_supported",
+           "blp_topk_relations_wide_bilinear_workspace_bytes", "blp_topk_relations_wide_bilinear",
            "blp_rerank_supported", "blp_rerank_cosine", "blp_rerank_ndcg")
 HOOK_SYMBOLS = ("blp_debug_set_knob", "blp_debug_gemm_dump", "blp_debug_reset_selftest", "blp_debug_topk_wide_lds_bytes")  # libblp_hip.hooks.so only
 KNOBS = ("rank_kernel", "gemm_kernel", "sad_queries_per_group", "sad_pass_groups", "sad_min_queries",
@@ -309,7 +312,13 @@ def _load(path, hooks):
                          (L.blp_rank_relations_wide, L.blp_rank_relations),
                          (L.blp_topk_relations_wide_supported, L.blp_topk_relations_supported),
                          (L.blp_topk_relations_wide_workspace_bytes, L.blp_topk_relations_workspace_bytes),
-                         (L.blp_topk_relations_wide, L.blp_topk_relations)):  # the narrow calls' signatures, by design
+                         (L.blp_topk_relations_wide, L.blp_topk_relations),
+                         (L.blp_rank_relations_wide_bilinear_supported, L.blp_rank_relations_supported),
+                         (L.blp_rank_relations_wide_bilinear_workspace_bytes, L.blp_rank_relations_workspace_bytes),
+                         (L.blp_rank_relations_wide_bilinear, L.blp_rank_relations),
+                         (L.blp_topk_relations_wide_bilinear_supported, L.blp_topk_relations_supported),
+                         (L.blp_topk_relations_wide_bilinear_workspace_bytes, L.blp_topk_relations_workspace_bytes),
+                         (L.blp_topk_relations_wide_bilinear, L.blp_topk_relations)):  # the narrow calls' signatures, by design
         wide.restype, wide.argtypes = narrow.restype, list(narrow.argtypes)
     L.blp_rerank_supported.restype = _i
     L.blp_rerank_supported.argtypes = [_i64, _i]

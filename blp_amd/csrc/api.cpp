@@ -1016,6 +1016,24 @@ size_t blp_topk_relations_wide_workspace_bytes(int model, int D, int64_t Q, int6
     return 0;  // as blp_topk_relations: lists in LDS, one owner per query, the winners' scores come out of the keys
 }
 
+int blp_rank_relations_wide_bilinear_supported(int model, int D) {
+    return valid_model(model) && blp::rank_relations_wide_bilinear_supported(model, D) ? 1 : 0;
+}
+
+size_t blp_rank_relations_wide_bilinear_workspace_bytes(int model, int D, int64_t Q, int64_t R) {
+    if (!blp_rank_relations_wide_bilinear_supported(model, D) || Q < 0 || Q > (1ll << 30) || R < 1 || R >= (1ll << 31)) return 0;
+    return blp::rank_relations_workspace_bytes(Q);
+}
+
+int blp_topk_relations_wide_bilinear_supported(int model, int D, int k) {
+    return valid_model(model) && blp::topk_relations_wide_bilinear_supported(model, D, k) ? 1 : 0;
+}
+
+size_t blp_topk_relations_wide_bilinear_workspace_bytes(int model, int D, int64_t Q, int64_t R, int k) {
+    (void)model; (void)D; (void)Q; (void)R; (void)k;
+    return 0;  // as blp_topk_relations_wide: lists in LDS, one owner per query, the winners' scores come out of the keys
+}
+
 namespace {
 
 // what the relation entries check alike: the queries, the candidates, the filter (its values are relation ids)
@@ -1043,15 +1061,22 @@ int check_relation_call(const char* who, int D, const float* source, int64_t S, 
     return BLP_OK;
 }
 
-// blp_rank_relations and blp_rank_relations_wide: the argument checks (messages under the entry's name `who`), then the launch
-int rank_relations_call(const char* who, bool wide, int model, const float* source, int64_t S, int D, int64_t ld_src,
+// which file's kernels a relation entry launches: rank_rels.hip, rank_rels_wide.hip, rank_rels_wide_bilinear.hip
+enum RelRoute { REL_FIXED, REL_WIDE, REL_WIDE_BILINEAR };
+const char* const kRelRouteTakes[] = {"64 / 128 / 256", "TransE, D % 4 == 0, 4 <= D <= 1024",
+                                      "DistMult / ComplEx / SimplE, D % 4 == 0, 4 <= D <= 1024"};
+
+// blp_rank_relations, blp_rank_relations_wide and blp_rank_relations_wide_bilinear: the argument checks (messages under the
+// entry's name `who`), then the launch
+int rank_relations_call(const char* who, RelRoute route, int model, const float* source, int64_t S, int D, int64_t ld_src,
                         const int64_t* head_row, const int64_t* tail_row, int64_t Q, const float* rel_emb, int64_t R,
                         const int64_t* true_rel, const blp_filter* filter, int32_t* counts, float* scores, int64_t ld_scores,
                         void* workspace, size_t workspace_bytes, int device, void* stream) {
     if (!valid_model(model)) return fail(BLP_ERR_BAD_ARG, "%s: unknown model %d", who, model);
-    if (!(wide ? blp_rank_relations_wide_supported(model, D) : blp_rank_relations_supported(model, D)))
-        return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (%s: see %s_supported)", who, D,
-                    wide ? "TransE, D % 4 == 0, 4 <= D <= 1024" : "64 / 128 / 256", who);
+    if (!(route == REL_WIDE_BILINEAR ? blp_rank_relations_wide_bilinear_supported(model, D)
+          : route == REL_WIDE        ? blp_rank_relations_wide_supported(model, D)
+                                     : blp_rank_relations_supported(model, D)))
+        return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (%s: see %s_supported)", who, D, kRelRouteTakes[route], who);
     blp::FilterSpec spec;
     const int st = check_relation_call(who, D, source, S, ld_src, head_row, tail_row, Q, rel_emb, R, filter, &spec);
     if (st != BLP_OK) return st;
@@ -1066,22 +1091,29 @@ int rank_relations_call(const char* who, bool wide, int model, const float* sour
         return fail(BLP_ERR_WORKSPACE, "%s: workspace must be 256-byte aligned and >= %zu bytes (got %zu)", who, need, workspace_bytes);
     DeviceGuard guard(device);
     if (guard.error() != hipSuccess) return hip_fail(guard.error(), "hipSetDevice");
-    hipError_t err = (wide ? blp::launch_rank_relations_wide : blp::launch_rank_relations)(
+    hipError_t err = (route == REL_WIDE_BILINEAR ? blp::launch_rank_relations_wide_bilinear
+                      : route == REL_WIDE        ? blp::launch_rank_relations_wide
+                                                 : blp::launch_rank_relations)(
         model, D, source, ld_src, head_row, tail_row, Q, rel_emb, R, counts ? true_rel : nullptr, spec, counts, scores, ld_scores, workspace,
         static_cast<hipStream_t>(stream));
-    if (err != hipSuccess) return hip_fail(err, wide ? "blp_rank_relations_wide launch" : "blp_rank_relations launch");
+    if (err != hipSuccess)
+        return hip_fail(err, route == REL_WIDE_BILINEAR ? "blp_rank_relations_wide_bilinear launch"
+                             : route == REL_WIDE        ? "blp_rank_relations_wide launch"
+                                                        : "blp_rank_relations launch");
     return BLP_OK;
 }
 
-// blp_topk_relations and blp_topk_relations_wide (neither uses its workspace: *_workspace_bytes() == 0)
-int topk_relations_call(const char* who, bool wide, int model, const float* source, int64_t S, int D, int64_t ld_src,
+// blp_topk_relations, blp_topk_relations_wide and blp_topk_relations_wide_bilinear (none uses its workspace:
+// *_workspace_bytes() == 0)
+int topk_relations_call(const char* who, RelRoute route, int model, const float* source, int64_t S, int D, int64_t ld_src,
                         const int64_t* head_row, const int64_t* tail_row, int64_t Q, const float* rel_emb, int64_t R, int k,
                         const blp_filter* filter, int64_t* rels, float* scores, int device, void* stream) {
     if (!valid_model(model)) return fail(BLP_ERR_BAD_ARG, "%s: unknown model %d", who, model);
     if (k < 1 || k > 256) return fail(BLP_ERR_BAD_ARG, "%s: k = %d outside [1, 256]", who, k);
-    if (!(wide ? blp_topk_relations_wide_supported(model, D, k) : blp_topk_relations_supported(model, D, k)))
-        return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (%s: see %s_supported)", who, D,
-                    wide ? "TransE, D % 4 == 0, 4 <= D <= 1024" : "64 / 128 / 256", who);
+    if (!(route == REL_WIDE_BILINEAR ? blp_topk_relations_wide_bilinear_supported(model, D, k)
+          : route == REL_WIDE        ? blp_topk_relations_wide_supported(model, D, k)
+                                     : blp_topk_relations_supported(model, D, k)))
+        return fail(BLP_ERR_UNSUPPORTED_DIM, "%s: D = %d not supported (%s: see %s_supported)", who, D, kRelRouteTakes[route], who);
     blp::FilterSpec spec;
     const int st = check_relation_call(who, D, source, S, ld_src, head_row, tail_row, Q, rel_emb, R, filter, &spec);
     if (st != BLP_OK) return st;
@@ -1091,9 +1123,14 @@ int topk_relations_call(const char* who, bool wide, int model, const float* sour
     if (Q == 0) return BLP_OK;
     DeviceGuard guard(device);
     if (guard.error() != hipSuccess) return hip_fail(guard.error(), "hipSetDevice");
-    hipError_t err = (wide ? blp::launch_topk_relations_wide : blp::launch_topk_relations)(
+    hipError_t err = (route == REL_WIDE_BILINEAR ? blp::launch_topk_relations_wide_bilinear
+                      : route == REL_WIDE        ? blp::launch_topk_relations_wide
+                                                 : blp::launch_topk_relations)(
         model, D, source, ld_src, head_row, tail_row, Q, rel_emb, R, k, spec, rels, scores, static_cast<hipStream_t>(stream));
-    if (err != hipSuccess) return hip_fail(err, wide ? "blp_topk_relations_wide launch" : "blp_topk_relations launch");
+    if (err != hipSuccess)
+        return hip_fail(err, route == REL_WIDE_BILINEAR ? "blp_topk_relations_wide_bilinear launch"
+                             : route == REL_WIDE        ? "blp_topk_relations_wide launch"
+                                                        : "blp_topk_relations launch");
     return BLP_OK;
 }
 
@@ -1102,7 +1139,7 @@ int topk_relations_call(const char* who, bool wide, int model, const float* sour
 int blp_rank_relations(int model, const float* source, int64_t S, int D, int64_t ld_src, const int64_t* head_row, const int64_t* tail_row,
                        int64_t Q, const float* rel_emb, int64_t R, const int64_t* true_rel, const blp_filter* filter, int32_t* counts,
                        float* scores, int64_t ld_scores, void* workspace, size_t workspace_bytes, int device, void* stream) {
-    return rank_relations_call("blp_rank_relations", false, model, source, S, D, ld_src, head_row, tail_row, Q, rel_emb, R, true_rel, filter,
+    return rank_relations_call("blp_rank_relations", REL_FIXED, model, source, S, D, ld_src, head_row, tail_row, Q, rel_emb, R, true_rel, filter,
                                counts, scores, ld_scores, workspace, workspace_bytes, device, stream);
 }
 
@@ -1110,7 +1147,7 @@ int blp_topk_relations(int model, const float* source, int64_t S, int D, int64_t
                        int64_t Q, const float* rel_emb, int64_t R, int k, const blp_filter* filter, int64_t* rels, float* scores,
                        void* workspace, size_t workspace_bytes, int device, void* stream) {
     (void)workspace; (void)workspace_bytes;  // blp_topk_relations_workspace_bytes() == 0
-    return topk_relations_call("blp_topk_relations", false, model, source, S, D, ld_src, head_row, tail_row, Q, rel_emb, R, k, filter, rels,
+    return topk_relations_call("blp_topk_relations", REL_FIXED, model, source, S, D, ld_src, head_row, tail_row, Q, rel_emb, R, k, filter, rels,
                                scores, device, stream);
 }
 
@@ -1119,7 +1156,7 @@ int blp_rank_relations_wide(int model, const float* source, int64_t S, int D, in
                             const int64_t* tail_row, int64_t Q, const float* rel_emb, int64_t R, const int64_t* true_rel,
                             const blp_filter* filter, int32_t* counts, float* scores, int64_t ld_scores, void* workspace,
                             size_t workspace_bytes, int device, void* stream) {
-    return rank_relations_call("blp_rank_relations_wide", true, model, source, S, D, ld_src, head_row, tail_row, Q, rel_emb, R, true_rel,
+    return rank_relations_call("blp_rank_relations_wide", REL_WIDE, model, source, S, D, ld_src, head_row, tail_row, Q, rel_emb, R, true_rel,
                                filter, counts, scores, ld_scores, workspace, workspace_bytes, device, stream);
 }
 
@@ -1127,8 +1164,26 @@ int blp_topk_relations_wide(int model, const float* source, int64_t S, int D, in
                             const int64_t* tail_row, int64_t Q, const float* rel_emb, int64_t R, int k, const blp_filter* filter,
                             int64_t* rels, float* scores, void* workspace, size_t workspace_bytes, int device, void* stream) {
     (void)workspace; (void)workspace_bytes;  // blp_topk_relations_wide_workspace_bytes() == 0
-    return topk_relations_call("blp_topk_relations_wide", true, model, source, S, D, ld_src, head_row, tail_row, Q, rel_emb, R, k, filter,
+    return topk_relations_call("blp_topk_relations_wide", REL_WIDE, model, source, S, D, ld_src, head_row, tail_row, Q, rel_emb, R, k, filter,
                                rels, scores, device, stream);
+}
+
+// ---- ... for DistMult / ComplEx / SimplE at any width (rank_rels_wide_bilinear.hip): the same arguments, checks and codes
+int blp_rank_relations_wide_bilinear(int model, const float* source, int64_t S, int D, int64_t ld_src, const int64_t* head_row,
+                                     const int64_t* tail_row, int64_t Q, const float* rel_emb, int64_t R, const int64_t* true_rel,
+                                     const blp_filter* filter, int32_t* counts, float* scores, int64_t ld_scores, void* workspace,
+                                     size_t workspace_bytes, int device, void* stream) {
+    return rank_relations_call("blp_rank_relations_wide_bilinear", REL_WIDE_BILINEAR, model, source, S, D, ld_src, head_row, tail_row, Q,
+                               rel_emb, R, true_rel, filter, counts, scores, ld_scores, workspace, workspace_bytes, device, stream);
+}
+
+int blp_topk_relations_wide_bilinear(int model, const float* source, int64_t S, int D, int64_t ld_src, const int64_t* head_row,
+                                     const int64_t* tail_row, int64_t Q, const float* rel_emb, int64_t R, int k,
+                                     const blp_filter* filter, int64_t* rels, float* scores, void* workspace, size_t workspace_bytes,
+                                     int device, void* stream) {
+    (void)workspace; (void)workspace_bytes;  // blp_topk_relations_wide_bilinear_workspace_bytes() == 0
+    return topk_relations_call("blp_topk_relations_wide_bilinear", REL_WIDE_BILINEAR, model, source, S, D, ld_src, head_row, tail_row, Q,
+                               rel_emb, R, k, filter, rels, scores, device, stream);
 }
 
 // ---- candidate sets shared between queries (rank_sets.hip)

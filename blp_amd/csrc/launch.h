@@ -187,6 +187,19 @@ hipError_t launch_topk_relations_wide(int model, int D, const float* source, int
                                       const int64_t* tail_row, int64_t Q, const float* rel_emb, int64_t R, int k, const FilterSpec& filter,
                                       int64_t* rels, float* scores, hipStream_t stream);
 
+// rank_rels_wide_bilinear.hip: the same two calls for DistMult / ComplEx / SimplE at any width (D % 4 == 0, 4 <= D <= 1024;
+// include/blp_hip.h: blp_rank_relations_wide_bilinear, blp_topk_relations_wide_bilinear): same arguments, same workspace
+// (rank_relations_workspace_bytes; top-k none)
+bool rank_relations_wide_bilinear_supported(int model, int D);
+hipError_t launch_rank_relations_wide_bilinear(int model, int D, const float* source, int64_t ld_src, const int64_t* head_row,
+                                               const int64_t* tail_row, int64_t Q, const float* rel_emb, int64_t R,
+                                               const int64_t* true_rel, const FilterSpec& filter, int32_t* counts, float* scores,
+                                               int64_t ld_scores, void* workspace, hipStream_t stream);
+bool topk_relations_wide_bilinear_supported(int model, int D, int k);
+hipError_t launch_topk_relations_wide_bilinear(int model, int D, const float* source, int64_t ld_src, const int64_t* head_row,
+                                               const int64_t* tail_row, int64_t Q, const float* rel_emb, int64_t R, int k,
+                                               const FilterSpec& filter, int64_t* rels, float* scores, hipStream_t stream);
+
 // rerank.hip: re-ranking a retrieval run (include/blp_hip.h: blp_rerank_cosine, blp_rerank_ndcg)
 constexpr int kRerankMaxSegment = 8192;  // candidates per query: 8 192 keys of 8 bytes = 64 KiB of LDS
 constexpr int kRerankMaxCutoffs = 8;

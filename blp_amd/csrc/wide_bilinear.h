@@ -131,6 +131,62 @@ struct WideTerm<SIMPLE, HEAD> {  // f = tail = [th | tt], e = head = [hh | ht]
     }
 };
 
+// A third side next to HEAD / TAIL (score_core.h): the candidates are RELATION rows (rank_rels_wide_bilinear.hip), f = the
+// pair's head vector, r = its tail vector.  The candidate sits in the middle of the reference's expressions, so nothing is
+// hoisted: the coefficients are the two vectors as they are, the operations those of rel_scorer.h / score_direct.h.
+constexpr int REL = 2;
+
+template <>
+struct WideTerm<DISTMULT, REL> {  // (h * e) * t
+    static constexpr int K = 2;
+    static constexpr bool kHalves = false;
+    __device__ __forceinline__ static float coef(const float* f, const float* r, int j, int H, int k) { return k == 0 ? f[j] : r[j]; }
+    __device__ __forceinline__ static float term(float ea, float eb, const float (&c)[K]) {
+        const float x = c[0] * ea;
+        return x * c[1];
+    }
+};
+template <>
+struct WideTerm<COMPLEX, REL> {  // e = [rr | ri]; hr, hi, tr, ti as they are
+    static constexpr int K = 4;
+    static constexpr bool kHalves = true;
+    __device__ __forceinline__ static float coef(const float* f, const float* r, int j, int H, int k) {
+        switch (k) {
+        case 0: return f[j];
+        case 1: return f[H + j];
+        case 2: return r[j];
+        default: return r[H + j];
+        }
+    }
+    __device__ __forceinline__ static float term(float ea, float eb, const float (&c)[K]) {
+        float a = ea * c[0];   a = a * c[2];    // (rr*hr)*tr
+        float b = ea * c[1];   b = b * c[3];    // (rr*hi)*ti
+        float cc = eb * c[0];  cc = cc * c[3];  // (ri*hr)*ti
+        float d = eb * c[1];   d = d * c[2];    // (ri*hi)*tr
+        float s = a + b;
+        s = s + cc;
+        return s - d;
+    }
+};
+template <>
+struct WideTerm<SIMPLE, REL> {  // f = head = [hh | ht], r = tail = [th | tt], e = [ra | rb]: (hh*ra)*tt + (th*rb)*ht
+    static constexpr int K = 4;
+    static constexpr bool kHalves = true;
+    __device__ __forceinline__ static float coef(const float* f, const float* r, int j, int H, int k) {
+        switch (k) {
+        case 0: return f[j];
+        case 1: return r[H + j];
+        case 2: return r[j];
+        default: return f[H + j];
+        }
+    }
+    __device__ __forceinline__ static float term(float ea, float eb, const float (&c)[K]) {
+        float a = c[0] * ea;  a = a * c[1];
+        float b = c[2] * eb;  b = b * c[3];
+        return a + b;
+    }
+};
+
 // terms of a score, and the floats of a coefficient array in LDS (n rounded up to whole 16-byte reads)
 __host__ __device__ inline int wide_terms(int model, int D) { return model == DISTMULT ? D : D / 2; }
 __host__ __device__ inline int wide_n4(int model, int D) { return (wide_terms(model, D) + 3) & ~3; }

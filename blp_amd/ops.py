@@ -966,17 +966,21 @@ def _relation_queries(source, head_row, tail_row, rel_emb, who):
     return source, head_row, tail_row, rel_emb
 
 
-def _rank_relations(wide, rel_model, source, head_row, tail_row, rel_emb, true_rel, filter, return_scores, out):
-    """rank_relations (blp_rank_relations) and rank_relations_wide (blp_rank_relations_wide): one argument handling, two entries."""
-    who = "rank_relations_wide" if wide else "rank_relations"
+_RELATION_ROUTES = {"": "64 / 128 / 256", "_wide": "transe, D % 4 == 0, 4 <= D <= 1024",
+                    "_wide_bilinear": "distmult / complex / simple, D % 4 == 0, 4 <= D <= 1024"}  # entry suffix -> what it takes
+
+
+def _rank_relations(route, rel_model, source, head_row, tail_row, rel_emb, true_rel, filter, return_scores, out):
+    """rank_relations (blp_rank_relations), rank_relations_wide (blp_rank_relations_wide) and rank_relations_wide_bilinear
+    (blp_rank_relations_wide_bilinear): one argument handling, three entries (``route``: the entry's suffix)."""
+    who = "rank_relations" + route
     source, head_row, tail_row, rel_emb = _relation_queries(source, head_row, tail_row, rel_emb, who)
     _require_device(true_rel)
     Q, (R, D) = head_row.shape[0], rel_emb.shape
     if true_rel is None and not return_scores:
         raise ValueError(f"{who}: give true_rel (counts), return_scores=True, or both")
-    if not (rank_relations_wide_supported if wide else rank_relations_supported)(rel_model, D):
-        raise ValueError(f"{who}: D = {D} not supported for {rel_model} "
-                         f"({'transe, D % 4 == 0, 4 <= D <= 1024' if wide else '64 / 128 / 256'}: see {who}_supported)")
+    if not getattr(_lib.lib(), f"blp_{who}_supported")(_lib.MODEL_IDS[rel_model], int(D)):
+        raise ValueError(f"{who}: D = {D} not supported for {rel_model} ({_RELATION_ROUTES[route]}: see {who}_supported)")
     if filter is not None and (filter.ent2idx is not None or int(filter.row_base) != 0):
         raise ValueError(f"{who}: the filter's values are relation ids (ent2idx None, row_base 0)")
     dev = source.device
@@ -992,7 +996,7 @@ def _rank_relations(wide, rel_model, source, head_row, tail_row, rel_emb, true_r
         scores = torch.empty((Q, R), dtype=torch.float32, device=dev)
     if Q:
         L = _lib.lib()
-        entry = "blp_rank_relations_wide" if wide else "blp_rank_relations"
+        entry = "blp_" + who
         model = _lib.MODEL_IDS[rel_model]
         stream = torch._C._cuda_getCurrentRawStream(dev.index)
         ws_bytes = getattr(L, entry + "_workspace_bytes")(model, D, Q, R) if counts is not None else 0
@@ -1008,15 +1012,15 @@ def _rank_relations(wide, rel_model, source, head_row, tail_row, rel_emb, true_r
     return (counts, scores) if return_scores else counts
 
 
-def _topk_relations(wide, rel_model, source, head_row, tail_row, rel_emb, k, filter, out):
-    """topk_relations (blp_topk_relations) and topk_relations_wide (blp_topk_relations_wide)."""
-    who = "topk_relations_wide" if wide else "topk_relations"
+def _topk_relations(route, rel_model, source, head_row, tail_row, rel_emb, k, filter, out):
+    """topk_relations (blp_topk_relations), topk_relations_wide (blp_topk_relations_wide) and topk_relations_wide_bilinear
+    (blp_topk_relations_wide_bilinear)."""
+    who = "topk_relations" + route
     source, head_row, tail_row, rel_emb = _relation_queries(source, head_row, tail_row, rel_emb, who)
     Q, (R, D) = head_row.shape[0], rel_emb.shape
     k = int(k)
-    if not (topk_relations_wide_supported if wide else topk_relations_supported)(rel_model, D, k):
-        raise ValueError(f"{who}: D = {D}, k = {k} not supported for {rel_model} "
-                         f"({'transe, D % 4 == 0, 4 <= D <= 1024' if wide else '64 / 128 / 256'}, 1 <= k <= 256)")
+    if not getattr(_lib.lib(), f"blp_{who}_supported")(_lib.MODEL_IDS[rel_model], int(D), k):
+        raise ValueError(f"{who}: D = {D}, k = {k} not supported for {rel_model} ({_RELATION_ROUTES[route]}, 1 <= k <= 256)")
     if filter is not None and (filter.ent2idx is not None or int(filter.row_base) != 0):
         raise ValueError(f"{who}: the filter's values are relation ids (ent2idx None, row_base 0)")
     dev = source.device
@@ -1029,7 +1033,7 @@ def _topk_relations(wide, rel_model, source, head_row, tail_row, rel_emb, k, fil
     if Q == 0:
         return rels, scores
     L = _lib.lib()
-    entry = "blp_topk_relations_wide" if wide else "blp_topk_relations"
+    entry = "blp_" + who
     model = _lib.MODEL_IDS[rel_model]
     stream = torch._C._cuda_getCurrentRawStream(dev.index)
     ws_bytes = getattr(L, entry + "_workspace_bytes")(model, D, Q, R, k)
@@ -1049,7 +1053,7 @@ def rank_relations(rel_model, source, head_row, tail_row, rel_emb, true_rel=None
     ge_filt}, the relations that score above / at least the true one, the last two without those ``filter`` (a SegmentFilter
     whose values are RELATION ids: no ent2idx, row_base 0; ``exclude`` is never removed) names.  ``return_scores``: the (Q, R)
     score matrix, score_fn's values bit for bit.  Returns counts, scores, or (counts, scores); ``out`` may give counts."""
-    return _rank_relations(False, rel_model, source, head_row, tail_row, rel_emb, true_rel, filter, return_scores, out)
+    return _rank_relations("", rel_model, source, head_row, tail_row, rel_emb, true_rel, filter, return_scores, out)
 
 
 def topk_relations(rel_model, source, head_row, tail_row, rel_emb, k, filter=None, out=None):
@@ -1058,7 +1062,7 @@ def topk_relations(rel_model, source, head_row, tail_row, rel_emb, k, filter=Non
     relations ``filter`` names removed (a SegmentFilter of relation ids, as in rank_relations); slots beyond the relations left
     (k > R, a filter that leaves fewer): -1, score NaN.  Returns (rels (Q, k) int64, scores (Q, k) float32); ``out`` may give
     both."""
-    return _topk_relations(False, rel_model, source, head_row, tail_row, rel_emb, k, filter, out)
+    return _topk_relations("", rel_model, source, head_row, tail_row, rel_emb, k, filter, out)
 
 
 def rank_relations_wide_supported(rel_model, dim):
@@ -1085,13 +1089,48 @@ def topk_relations_wide_workspace_bytes(rel_model, D, Q, R, k):
 def rank_relations_wide(rel_model, source, head_row, tail_row, rel_emb, true_rel=None, filter=None, return_scores=False, out=None):
     """rank_relations for TransE at any width D % 4 == 0, 4 <= D <= 1024 (blp_rank_relations_wide: a lane holds 64 columns of
     its relation row at a time and carries the running sums): the same arguments, the same counts and score bits."""
-    return _rank_relations(True, rel_model, source, head_row, tail_row, rel_emb, true_rel, filter, return_scores, out)
+    return _rank_relations("_wide", rel_model, source, head_row, tail_row, rel_emb, true_rel, filter, return_scores, out)
 
 
 def topk_relations_wide(rel_model, source, head_row, tail_row, rel_emb, k, filter=None, out=None):
     """topk_relations for TransE at any width D % 4 == 0, 4 <= D <= 1024 (blp_topk_relations_wide): the same arguments, order,
     padding and score bits."""
-    return _topk_relations(True, rel_model, source, head_row, tail_row, rel_emb, k, filter, out)
+    return _topk_relations("_wide", rel_model, source, head_row, tail_row, rel_emb, k, filter, out)
+
+
+def rank_relations_wide_bilinear_supported(rel_model, dim):
+    """True if rank_relations_wide_bilinear takes this width (blp_rank_relations_wide_bilinear_supported: distmult / complex /
+    simple, D % 4 == 0, 4 <= D <= 1024 -- the BOW / DKRL encoders' 300 and 768 among them)."""
+    return bool(_lib.lib().blp_rank_relations_wide_bilinear_supported(_lib.MODEL_IDS[rel_model], int(dim)))
+
+
+def rank_relations_wide_bilinear_workspace_bytes(rel_model, D, Q, R):
+    """Bytes of rank_relations_wide_bilinear's workspace: the Q true-relation keys (4 Q rounded up to 256), whatever R and D."""
+    return int(_lib.lib().blp_rank_relations_wide_bilinear_workspace_bytes(_lib.MODEL_IDS[rel_model], int(D), int(Q), int(R)))
+
+
+def topk_relations_wide_bilinear_supported(rel_model, dim, k):
+    """True if topk_relations_wide_bilinear takes this width and k (rank_relations_wide_bilinear's widths, 1 <= k <= 256)."""
+    return bool(_lib.lib().blp_topk_relations_wide_bilinear_supported(_lib.MODEL_IDS[rel_model], int(dim), int(k)))
+
+
+def topk_relations_wide_bilinear_workspace_bytes(rel_model, D, Q, R, k):
+    """Bytes of topk_relations_wide_bilinear's workspace: 0 (the lists live on chip, every query has one owner)."""
+    return int(_lib.lib().blp_topk_relations_wide_bilinear_workspace_bytes(_lib.MODEL_IDS[rel_model], int(D), int(Q), int(R), int(k)))
+
+
+def rank_relations_wide_bilinear(rel_model, source, head_row, tail_row, rel_emb, true_rel=None, filter=None, return_scores=False,
+                                 out=None):
+    """rank_relations for DistMult / ComplEx / SimplE at any width D % 4 == 0, 4 <= D <= 1024 (blp_rank_relations_wide_bilinear:
+    eight lanes per relation row restate torch's sum order, eight pairs per workgroup pass): the same arguments, the same counts
+    and score bits."""
+    return _rank_relations("_wide_bilinear", rel_model, source, head_row, tail_row, rel_emb, true_rel, filter, return_scores, out)
+
+
+def topk_relations_wide_bilinear(rel_model, source, head_row, tail_row, rel_emb, k, filter=None, out=None):
+    """topk_relations for DistMult / ComplEx / SimplE at any width D % 4 == 0, 4 <= D <= 1024 (blp_topk_relations_wide_bilinear):
+    the same arguments, order, padding and score bits."""
+    return _topk_relations("_wide_bilinear", rel_model, source, head_row, tail_row, rel_emb, k, filter, out)
 
 
 def topk_merge(rows, scores, k):

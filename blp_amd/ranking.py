@@ -999,10 +999,13 @@ def rank_relations(model, table, triples, ent2idx, *, filter_index=None, return_
     filter_index utils.RelationFilterIndex of the known edges: the other known relations of the pair leave the filtered counts
     Returns counts (T, 4) int32 = {gt, ge, gt_filt, ge_filt} -- relations scoring above / at least the true one, IEEE
     comparison, the true relation itself included in ge; metrics_from_counts applies unchanged -- and, with ``return_scores``,
-    the (T, R) score_fn values bit for bit.  HIP tensors at a width blp_rank_relations takes (64 / 128 / 256), or of a TransE
-    model at any width blp_rank_relations_wide takes (D % 4 == 0, 4 <= D <= 1024: the BOW / DKRL 300 and 768): the fused kernel
-    (no (T, R) matrix unless asked for); CPU tensors and everything else: score_fn broadcast over the relations in bounded
-    pieces.  The routes give the same bits."""
+    the (T, R) score_fn values bit for bit.  HIP tensors at a width blp_rank_relations takes (64 / 128 / 256), or at any other
+    width D % 4 == 0, 4 <= D <= 1024 (the BOW / DKRL 300 and 768) -- blp_rank_relations_wide for a TransE model,
+    blp_rank_relations_wide_bilinear for DistMult / ComplEx / SimplE: the fused kernel (no (T, R) matrix unless asked for); CPU
+    tensors and everything else: score_fn broadcast over the relations in bounded pieces.  The fused kernels give the C
+    oracle's bits (torch's sum(dim=-1) order of a single score); the routes give the same bits wherever the CPU dense route
+    equals the oracle.  One exception is known: ComplEx / SimplE at D = 12, where torch's broadcast reduction adds the 6 terms
+    in another order than its reduction of one row (tests/test_rank_relations_wide_bilinear_host.py pins it)."""
     model = _module(model)
     triples, head_rows, tail_rows, rel_w = _relation_queries(model, table, triples, ent2idx, "rank_relations", 3)
     device, T, R = table.device, triples.shape[0], rel_w.shape[0]
@@ -1012,6 +1015,8 @@ def rank_relations(model, table, triples, ent2idx, *, filter_index=None, return_
         fused = ops.rank_relations
     elif table.is_cuda and ops.rank_relations_wide_supported(model.rel_model, table.shape[1]):
         fused = ops.rank_relations_wide
+    elif table.is_cuda and ops.rank_relations_wide_bilinear_supported(model.rel_model, table.shape[1]):
+        fused = ops.rank_relations_wide_bilinear
     if fused is not None:
         source, hr, tr = _relation_source(table, triples, ent2idx, head_rows, tail_rows)
         return fused(model.rel_model, source, hr, tr, rel_w, triples[:, 2].contiguous(), filter=filt, return_scores=return_scores)
@@ -1036,8 +1041,10 @@ def predict_relations(model, table, pairs, k, ent2idx, *, filter_index=None):
     are REMOVED, except the row's third column when there is one (-1 there removes every known relation, as two columns do).
     Returns (rels (T, k) int64, scores (T, k) float32): descending score, ties by ascending relation id, NaN last; -1 / NaN
     beyond the relations left (k may exceed R).  Scores are score_fn's values bit for bit.  HIP tensors at a width
-    blp_topk_relations takes -- or, a TransE model, blp_topk_relations_wide (D % 4 == 0, 4 <= D <= 1024) -- and k <= 256: the
-    fused kernel; otherwise score_fn broadcast in bounded pieces + the stable order (also the fused routes' oracle)."""
+    blp_topk_relations takes -- or at any other D % 4 == 0, 4 <= D <= 1024: blp_topk_relations_wide for a TransE model,
+    blp_topk_relations_wide_bilinear for DistMult / ComplEx / SimplE -- and k <= 256: the fused kernel; otherwise (CPU tensors,
+    k > 256) score_fn broadcast in bounded pieces + the stable order.  The routes give the same bits wherever the CPU dense
+    route equals the C oracle (rank_relations names the one known exception, ComplEx / SimplE at D = 12)."""
     model = _module(model)
     k = int(k)
     if k < 1:
@@ -1050,6 +1057,8 @@ def predict_relations(model, table, pairs, k, ent2idx, *, filter_index=None):
         fused = ops.topk_relations
     elif table.is_cuda and ops.topk_relations_wide_supported(model.rel_model, table.shape[1], k):
         fused = ops.topk_relations_wide
+    elif table.is_cuda and ops.topk_relations_wide_bilinear_supported(model.rel_model, table.shape[1], k):
+        fused = ops.topk_relations_wide_bilinear
     if fused is not None:
         source, hr, tr = _relation_source(table, pairs, ent2idx, head_rows, tail_rows)
         return fused(model.rel_model, source, hr, tr, rel_w, k, filter=filt)

@@ -934,6 +934,43 @@ int blp_topk_relations_wide(int model, const float *source, int64_t S, int D, in
                             int device, void *stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Relation prediction for DistMult / ComplEx / SimplE at ANY width: blp_rank_relations_wide_bilinear and
+ * blp_topk_relations_wide_bilinear are blp_rank_relations and blp_topk_relations -- the same argument lists, the same outputs
+ * bit for bit (counts {gt, ge, gt_filt, ge_filt}; scores (Q, R) with ld_scores, the torch-CPU order of oracle/blp_oracle.c,
+ * sign of zero included; counts only, scores only or both; top-k order, padding, NaN as 0x7fc00000, removed relations
+ * removed, k > R legal), the same filter rules (values are relation ids, ent2idx NULL, row_base 0, exclude[q] never
+ * removed), argument checks, error codes, messages and order of checks -- at the widths the BOW / DKRL encoders train the
+ * bilinear models at (300, 768).  A caller switches by name.
+ * Limits: BLP_MODEL_DISTMULT / BLP_MODEL_COMPLEX / BLP_MODEL_SIMPLE, D % 4 == 0 and 4 <= D <= 1024
+ *   (blp_rank_relations_wide_bilinear_supported; the top-k call also 1 <= k <= 256); TransE and any other width:
+ *   BLP_ERR_UNSUPPORTED_DIM.  64 / 128 / 256 are inside the rule, as a second implementation of the same bits.  Everything
+ *   else as above: 1 <= R < 2^31; Q <= 2^30; Q x k < 2^31; source / rel_emb / outputs 16-byte aligned, ld_src % 4 == 0,
+ *   ld_src >= D; Q = 0 succeeds and touches nothing; every check runs before a device is touched.
+ * Workspace, 256-B aligned: blp_rank_relations_wide_bilinear_workspace_bytes = 4 Q bytes rounded up to 256 (the true
+ *   relations' keys; used with counts only: a scores-only call accepts NULL), whatever R and D;
+ *   blp_topk_relations_wide_bilinear_workspace_bytes = 0, NULL accepted (one owning workgroup per query, its k-lists in
+ *   on-chip memory; the winners' scores are written from the selection keys, which carry them exactly).  Both answer 0 where
+ *   unsupported or a size is negative.
+ * The sum of a score is torch's sum(dim=-1) order restated by eight lanes per relation row (the arithmetic of
+ * blp_rank_all_wide, the relation row in the candidate's place).
+ * Asynchronous on `stream`, no host synchronisation, no allocation, no global atomics.  Deterministic; nothing depends on the
+ * grid.
+ * (Added after 6.0.0 without a version change: no existing entry point changed.)
+ * -------------------------------------------------------------------------------------------- */
+int blp_rank_relations_wide_bilinear_supported(int model, int D);
+size_t blp_rank_relations_wide_bilinear_workspace_bytes(int model, int D, int64_t Q, int64_t R);
+int blp_rank_relations_wide_bilinear(int model, const float *source, int64_t S, int D, int64_t ld_src, const int64_t *head_row,
+                                     const int64_t *tail_row, int64_t Q, const float *rel_emb, int64_t R, const int64_t *true_rel,
+                                     const blp_filter *filter, int32_t *counts, float *scores, int64_t ld_scores, void *workspace,
+                                     size_t workspace_bytes, int device, void *stream);
+int blp_topk_relations_wide_bilinear_supported(int model, int D, int k);
+size_t blp_topk_relations_wide_bilinear_workspace_bytes(int model, int D, int64_t Q, int64_t R, int k);
+int blp_topk_relations_wide_bilinear(int model, const float *source, int64_t S, int D, int64_t ld_src, const int64_t *head_row,
+                                     const int64_t *tail_row, int64_t Q, const float *rel_emb, int64_t R, int k,
+                                     const blp_filter *filter, int64_t *rels, float *scores, void *workspace,
+                                     size_t workspace_bytes, int device, void *stream);
+
+/* --------------------------------------------------------------------------------------------
  * Re-ranking a first-stage retrieval run (reference retrieval.py rerank: BM25F candidates of DBpedia-Entity v2 re-scored
  * with entity embeddings, the mixing weight alpha chosen per fold by nDCG@100).  Candidates are a CSR over Q queries:
  * query q owns candidates [cand_ptr[q], cand_ptr[q + 1]) (cand_ptr (Q + 1) int64, cand_ptr[0] = 0, cand_ptr[Q] = C).

@@ -7,10 +7,11 @@ routes are compared before anything is timed; the two calls then alternate step 
 events: --warmup steps, then --steps steps, the median taken; that five times over.  One JSON line per workload: the median of
 the five medians of both routes, their ratio, the spread of the five medians ((max - min) / median) and the fraction of the f32
 lane-op roof (78.6 T lane-ops/s) at 3 lane-ops per (pair, column) -- TransE: add, subtract, add |x|; DistMult: multiply,
-multiply, add.
+multiply, add; SimplE: four multiplies and two adds per pair of columns -- and 6 for ComplEx (eight multiplies and four adds per
+pair of columns).
 
     python tools/rank_relations_bench.py [--steps 30] [--warmup 3] [--repeats 5] [--only NAME ...] [--out FILE.jsonl]
-                                         [--width D ...]
+                                         [--width D ...] [--model M ...]
 
   fb15k237-{transe,distmult}     310 116 pairs over a 14 541 x 128 table, R = 237
   wikidata5m-{transe,distmult}   1 000 000 pairs over 100 000 x 128 gathered rows, R = 822
@@ -19,6 +20,8 @@ multiply, add.
 (blp_rank_relations_wide / blp_topk_relations_wide; the BOW / DKRL encoders train TransE at 300 and 768), as workload
 fb15k237-transe-wide<D>, against the same yardstick.  At a width the register kernels take as well (64 / 128 / 256) they join the
 alternation (register_counts / register_topk) and the line carries the wide call's time over theirs: the cost of the slab form.
+--model M ... (with --width; default transe): the same shape for these models, distmult / complex / simple through
+blp_rank_relations_wide_bilinear / blp_topk_relations_wide_bilinear, as workload fb15k237-<model>-wide<D>.
 """
 import argparse
 import json
@@ -41,7 +44,7 @@ WORKLOADS = {
 K = 10
 PIECE_BYTES = 1 << 28
 ROOF_LANE_OPS = 78.6e12
-OPS_PER_COLUMN = 3
+OPS_PER_COLUMN = {"transe": 3, "distmult": 3, "complex": 6, "simple": 3}
 
 
 def measure(calls, steps, warmup):
@@ -84,7 +87,10 @@ def run(name, cfg, steps, warmup, repeats, wide=False):
     rels = rel_w.unsqueeze(0)
     owner = torch.arange(Q, device=dev).repeat_interleave(2)
     res = {}
-    rank_fn, topk_fn = (ops.rank_relations_wide, ops.topk_relations_wide) if wide else (ops.rank_relations, ops.topk_relations)
+    rank_fn, topk_fn = (ops.rank_relations, ops.topk_relations)
+    if wide:
+        rank_fn, topk_fn = (ops.rank_relations_wide, ops.topk_relations_wide) if model == "transe" else \
+            (ops.rank_relations_wide_bilinear, ops.topk_relations_wide_bilinear)
 
     def matrix(a, b):
         return ops.score(model, source[hr[a:b]].unsqueeze(1), source[tr[a:b]].unsqueeze(1), rels)
@@ -134,7 +140,7 @@ def run(name, cfg, steps, warmup, repeats, wide=False):
         calls.update(register_counts=register_counts, register_topk=register_topk)
     runs = [measure(calls, steps, warmup) for _ in range(repeats)]
     s = {n: summary([r[n] for r in runs]) for n in runs[0]}
-    lane_ops = Q * R * D * OPS_PER_COLUMN
+    lane_ops = Q * R * D * OPS_PER_COLUMN[model]
     roof = lambda n: round(lane_ops / (s[n]["median_ms"] * 1e-3) / ROOF_LANE_OPS, 4)
     if "register_counts" in s:
         extra["counts_wide_over_register"] = round(s["fused_counts"]["median_ms"] / s["register_counts"]["median_ms"], 2)
@@ -153,11 +159,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--only", nargs="*")
     ap.add_argument("--out")
-    ap.add_argument("--width", type=int, nargs="*", help="fb15k237-transe at these widths through the any-width calls")
+    ap.add_argument("--width", type=int, nargs="*", help="the fb15k237 shape at these widths through the any-width calls")
+    ap.add_argument("--model", nargs="*", default=["transe"], choices=sorted(OPS_PER_COLUMN), help="with --width: these models")
     args = ap.parse_args()
     workloads = WORKLOADS
     if args.width:
-        workloads = {f"fb15k237-transe-wide{D}": dict(WORKLOADS["fb15k237-transe"], D=D) for D in args.width}
+        workloads = {f"fb15k237-{m}-wide{D}": dict(WORKLOADS["fb15k237-transe"], model=m, D=D) for m in args.model for D in args.width}
     for name, cfg in workloads.items():
         if args.only and name not in args.only:
             continue
